@@ -33,6 +33,22 @@ original 100-job shape structurally caps published events at ~2k/s
 target no matter how fast the daemon is; 550 leaves ~10%% headroom over
 the target. The 100-job shape and the full capacity curve (ceiling
 ~20k ev/s at 1200 jobs) are in profiles/capacity.md.
+
+--dump-outputs DIR writes what the last timed step measured, between
+scrapes at the step's two edges, as DIR/<name>.npy in float64: which
+event series (per job: check exit + healthy status; per watch: changed +
+healthy) published during the step. Counts in a wall-clock window jitter
+from run to run; which series publish is determined by the inputs (the
+generated stress config, which depends only on the arguments), so two
+runs and two builds can be compared output for output.
+
+Set-up validates the generated config in-process through the native
+library (the daemon's own config code) before the daemon is started.
+
+A plain run does nothing beyond set-up, warmup, the timed steps and the
+result line; every figure in that line comes from the scrapes at the
+edges of the timed window. --full is where measurements that need runs
+of their own belong; there are none today, so it changes nothing.
 """
 
 import argparse
@@ -47,7 +63,7 @@ import urllib.request
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from containerpilot_amd import harness
+from containerpilot_amd import harness, native
 from containerpilot_amd.mockconsul import MockConsul
 
 BASELINE_EVENTS_PER_SEC = 10000.0  # >=10k events/sec target
@@ -94,10 +110,11 @@ def scrape(port):
     url = "http://127.0.0.1:%d/metrics" % port
     with urllib.request.urlopen(url, timeout=10) as resp:
         text = resp.read().decode()
-    published = 0.0
-    for m in re.finditer(r'^containerpilot_events\{[^}]*\} ([0-9.e+]+)$',
-                         text, re.M):
-        published += float(m.group(1))
+    series = {}
+    for m in re.finditer(r'^containerpilot_events\{code="([^"]*)",'
+                         r'source="([^"]*)"\} ([0-9.e+]+)$', text, re.M):
+        series[(m.group(1), m.group(2))] = float(m.group(3))
+    published = sum(series.values())
     delivered = 0.0
     m = re.search(r'^containerpilot_event_deliveries ([0-9.e+]+)$', text, re.M)
     if m:
@@ -108,7 +125,7 @@ def scrape(port):
             r'([0-9.e+]+)$', text, re.M):
         buckets[m.group(1)] = float(m.group(2))
     return {"published": published, "delivered": delivered,
-            "buckets": buckets}
+            "buckets": buckets, "series": series}
 
 
 def histogram_p99(b0, b1):
@@ -128,6 +145,51 @@ def histogram_p99(b0, b1):
         if cum >= target:
             return float("inf") if le == "+Inf" else float(le)
     return None
+
+
+def expected_series(n_jobs, n_watches):
+    """The (code, source) event series the stress config can publish in
+    steady state, in a fixed order: per job the health check's exit and
+    the job's healthy status, per watch its change and healthy status."""
+    jobs = [[("ExitSuccess", "check.svc-%03d" % i),
+             ("StatusHealthy", "svc-%03d" % i)] for i in range(n_jobs)]
+    watches = [[("StatusChanged", "watch.upstream-%02d" % i),
+                ("StatusHealthy", "watch.upstream-%02d" % i)]
+               for i in range(n_watches)]
+    return jobs, watches
+
+
+def dump_outputs(outdir, rank, n_jobs, n_watches, s_prev, s_now):
+    """Write what the last timed step measured, between the scrapes at
+    its two edges, as float64 .npy arrays. Event counts in a wall-clock
+    window jitter from run to run, so the arrays hold what the inputs
+    determine: which event series published during the step (1.0) and
+    which stayed silent (0.0). Rank 0 writes <name>.npy; other ranks of
+    a multi-rank run write <name>.rankN.npy."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    active = {key for key, count in s_now["series"].items()
+              if count > s_prev["series"].get(key, 0.0)}
+    jobs, watches = expected_series(n_jobs, n_watches)
+    expected = {key for row in jobs + watches for key in row}
+    arrays = {
+        # [n_jobs, 2]: check exited 0, job reported healthy (all 1.0
+        # while every check runs at least once per step)
+        "job_series_active_last_step":
+            [[float(key in active) for key in row] for row in jobs],
+        # [n_watches, 2]: upstream changed, upstream became healthy
+        # (all 0.0: the upstream set is stable after start-up)
+        "watch_series_active_last_step":
+            [[float(key in active) for key in row] for row in watches],
+        # [1]: 1.0 if anything else published (failed or timed-out
+        # checks, unhealthy status, ...)
+        "other_series_active_last_step": [float(bool(active - expected))],
+    }
+    suffix = "" if rank == 0 else ".rank%d" % rank
+    for name, values in arrays.items():
+        shape = (-1, 2) if name != "other_series_active_last_step" else (1,)
+        np.save(os.path.join(outdir, name + suffix + ".npy"),
+                np.asarray(values, dtype=np.float64).reshape(shape))
 
 
 def cgroup_cpu_info():
@@ -174,6 +236,14 @@ def run_rank(args, rank):
     cfg = stress_config(consul.address, telemetry_port, args.jobs,
                         args.watches, args.check_ms,
                         os.path.join(workdir, "cp.socket"))
+    # check the generated config in-process with the daemon's own config
+    # code (the native library), so a bad shape fails here with its
+    # message instead of as a daemon that never comes up
+    err = native.validate_config(json.dumps(cfg))
+    if err is not None:
+        consul.stop()
+        os.rmdir(workdir)
+        raise RuntimeError("stress config rejected: " + err)
     daemon = harness.Daemon(config_dict=cfg, workdir=workdir)
     daemon.start()
     daemon.wait_for_socket(timeout=30)
@@ -192,16 +262,27 @@ def main():
     parser.add_argument("--jobs", type=int, default=550)
     parser.add_argument("--watches", type=int, default=50)
     parser.add_argument("--check-ms", type=int, default=100)
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="write what the last timed step measured "
+                             "as DIR/<name>.npy (float64)")
+    parser.add_argument("--full", action="store_true",
+                        help="also run the measurements that need runs "
+                             "of their own (none today: every reported "
+                             "figure comes from the timed window)")
     args = parser.parse_args()
+    if args.steps < 1:
+        parser.error("--steps must be >= 1")
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     distributed = world_size > 1
 
-    import torch
-    import torch.distributed as dist
     if distributed:
-        # the workload is host-side; gloo coordinates ranks on any box
+        # torch is only the rank-coordination layer (the workload is
+        # host-side; gloo coordinates ranks on any box), so a plain
+        # single-process run does not pay for importing it
+        import torch
+        import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group(backend="gloo", rank=rank,
                                 world_size=world_size)
@@ -215,14 +296,23 @@ def main():
         def sync():
             if distributed:
                 dist.barrier()
-            if torch.cuda.is_available():
-                torch.cuda.synchronize()
+                if torch.cuda.is_available():
+                    torch.cuda.synchronize()
 
         sync()
         quota_cores, throttled0 = cgroup_cpu_info()
         t0 = time.monotonic()
         s0 = scrape(port)
-        time.sleep(args.steps)
+        # K timed steps of one second each, on deadlines from a common
+        # origin so per-step oversleep does not accumulate; the extra
+        # scrape at the opening edge of the last step is what
+        # --dump-outputs reports
+        origin = time.monotonic()
+        s_last = s0
+        for step in range(1, args.steps + 1):
+            if step == args.steps and step > 1:
+                s_last = scrape(port)
+            time.sleep(max(0.0, origin + step - time.monotonic()))
         sync()
         s1 = scrape(port)
         t1 = time.monotonic()
@@ -236,10 +326,13 @@ def main():
         p99 = histogram_p99(s0["buckets"], s1["buckets"])
         p99_ms = None if p99 is None else p99 * 1e3
 
-        local = torch.tensor(
-            [delivered, published, elapsed, p99_ms or 0.0],
-            dtype=torch.float64)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, args.jobs, args.watches,
+                         s_last, s1)
+
+        local = [delivered, published, elapsed, p99_ms or 0.0]
         if distributed:
+            local = torch.tensor(local, dtype=torch.float64)
             gathered = [torch.zeros_like(local) for _ in range(world_size)]
             dist.all_gather(gathered, local)
         else:

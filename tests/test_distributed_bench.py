@@ -20,7 +20,7 @@ def test_torchrun_two_ranks():
          "--master-addr", "127.0.0.1", "--master-port", "29537",
          os.path.join(REPO_ROOT, "bench.py"),
          "--gpus", "2", "--steps", "3", "--warmup", "1",
-         "--jobs", "20", "--watches", "5"],
+         "--jobs", "20", "--watches", "5", "--full"],
         capture_output=True, text=True, timeout=600, env=env,
         cwd=REPO_ROOT)
     assert result.returncode == 0, result.stdout + result.stderr

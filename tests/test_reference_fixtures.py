@@ -1,9 +1,10 @@
 """Config fidelity against the reference's own test fixture corpus.
 
-The fixtures are read from the read-only reference checkout at test
-time (never copied into this repo); when the checkout is absent (e.g.
-on the GPU box) these tests skip. Expected outcomes mirror the
-reference's own unit tests (jobs/config_test.go, watches/config_test.go,
+The fixtures are the reference's JSON5 config files (settings only, no
+program text), stored verbatim under tests/golden/reference_configs/
+with the reference's own directory layout, so the tests run from any
+checkout. Expected outcomes mirror the reference's own unit tests
+(jobs/config_test.go, watches/config_test.go,
 telemetry/telemetry_config_test.go).
 """
 
@@ -14,10 +15,8 @@ import pytest
 
 from containerpilot_amd import native
 
-REF = "/root/reference"
-
-pytestmark = pytest.mark.skipif(
-    not os.path.isdir(REF), reason="reference checkout not available")
+REF = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                   "golden", "reference_configs")
 
 
 def load(rel):
