@@ -11,6 +11,8 @@ import time
 
 from . import BINARY, REPO_ROOT
 
+SINK_BINARY = os.path.join(REPO_ROOT, "bin", "cpilot_probesink")
+
 
 def build(force=False):
     """Build the daemon + unit test binary with cmake/ninja (idempotent)."""
@@ -24,6 +26,49 @@ def build(force=False):
     subprocess.run(["ninja", "-C", build_dir], check=True,
                    capture_output=True)
     return BINARY
+
+
+class ProbeSink:
+    """A running bin/cpilot_probesink: the peer for native health probes
+    under test or under load. Modes: accept, http200, http503, hang,
+    split, close."""
+
+    def __init__(self, mode):
+        self.mode = mode
+        self.proc = None
+        self.port = None
+
+    def start(self):
+        # build() returns early once the daemon binary exists; a tree
+        # built before the sink was added needs the build forced
+        build(force=not os.path.exists(SINK_BINARY))
+        self.proc = subprocess.Popen([SINK_BINARY, self.mode],
+                                     stdout=subprocess.PIPE, text=True)
+        self.port = int(self.proc.stdout.readline())
+        return self
+
+    def accepted(self):
+        """Connections accepted so far (not available in `close` mode,
+        which never reads a request)."""
+        s = socket.create_connection(("127.0.0.1", self.port), timeout=5)
+        s.sendall(b"GET /__sink/stats HTTP/1.1\r\nHost: sink\r\n\r\n")
+        resp = b""
+        while True:
+            chunk = s.recv(4096)
+            if not chunk:
+                break
+            resp += chunk
+        s.close()
+        return json.loads(resp.partition(b"\r\n\r\n")[2])["accepted"]
+
+    def stop(self):
+        """SIGTERM the sink; returns its final accepted count."""
+        if self.proc is None:
+            return None
+        self.proc.terminate()
+        out, _ = self.proc.communicate(timeout=10)
+        self.proc = None
+        return json.loads(out)["accepted"] if out.strip() else None
 
 
 class Daemon:

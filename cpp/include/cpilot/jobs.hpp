@@ -21,6 +21,7 @@
 #include "cpilot/discovery.hpp"
 #include "cpilot/events.hpp"
 #include "cpilot/json.hpp"
+#include "cpilot/probe.hpp"
 #include "cpilot/timing.hpp"
 
 namespace cpilot {
@@ -52,6 +53,8 @@ struct JobConfig {
 
   // health checking
   CommandPtr healthCheckExec;
+  // native check (health.tcp / health.http), exclusive with the exec
+  health::ProbePtr healthProbe;
   Duration heartbeatInterval{0};
   int ttl = 0;
 
@@ -142,6 +145,7 @@ class Job : public Subscriber, public std::enable_shared_from_this<Job> {
   JobStatus status_ = JobStatus::Idle;
   std::shared_ptr<ServiceDefinition> service_;
   CommandPtr healthCheckExec_;
+  health::ProbePtr healthProbe_;
 
   Event startEvent_;
   Duration startTimeout_{0};

@@ -202,7 +202,8 @@ bool validateHealthCheck(const Json& raw, std::shared_ptr<JobConfig>& cfg,
     return false;
   }
   if (!decode::checkKeys(*health,
-                         {"exec", "timeout", "interval", "ttl", "logging"},
+                         {"exec", "http", "tcp", "timeout", "interval", "ttl",
+                          "logging"},
                          err)) {
     *err = "job configuration error: " + *err;
     return false;
@@ -252,6 +253,50 @@ bool validateHealthCheck(const Json& raw, std::shared_ptr<JobConfig>& cfg,
   }
 
   const Json* checkExec = health->find("exec");
+  const Json* checkHttp = health->find("http");
+  const Json* checkTcp = health->find("tcp");
+  auto given = [](const Json* v) { return v && !v->isNull(); };
+  if (given(checkExec) + given(checkHttp) + given(checkTcp) > 1) {
+    *err = "job[" + cfg->name +
+           "].health can have only one of 'exec', 'http', or 'tcp'";
+    return false;
+  }
+  if (given(checkHttp) || given(checkTcp)) {
+    // native probes: run on the reactor, nothing is spawned, so there is
+    // no child output to wrap or pass through
+    if (given(health->find("logging"))) {
+      *err = "job[" + cfg->name + "].health.logging only applies to "
+             "'exec' checks; 'http' and 'tcp' checks have no output";
+      return false;
+    }
+    health::ProbeSpec spec;
+    std::string probeErr;
+    if (given(checkTcp)) {
+      if (!checkTcp->isString()) {
+        *err = "job[" + cfg->name + "].health.tcp must be a \"HOST:PORT\" "
+               "string";
+        return false;
+      }
+      if (!health::parseTcpProbe(checkTcp->str(), &spec, &probeErr)) {
+        *err = "job[" + cfg->name + "].health.tcp '" + checkTcp->str() +
+               "': " + probeErr;
+        return false;
+      }
+    } else {
+      std::string key;
+      if (!health::parseHttpProbe(*checkHttp, &spec, &key, &probeErr)) {
+        *err = "job[" + cfg->name + "].health.http" + key + ": " + probeErr;
+        return false;
+      }
+    }
+    // a probe always runs under a deadline: an explicit zero timeout
+    // falls back to the interval like an absent one
+    spec.timeout =
+        checkTimeout > Duration(0) ? checkTimeout : cfg->heartbeatInterval;
+    cfg->healthProbe = std::make_shared<health::Probe>(
+        std::move(spec), "check." + cfg->name);
+    return true;
+  }
   if (checkExec && !checkExec->isNull()) {
     std::string checkName = "check." + cfg->name;
     bool raw_ = false;
@@ -503,6 +548,7 @@ Job::Job(const std::shared_ptr<JobConfig>& cfg)
       exec_(cfg->exec),
       service_(cfg->serviceDefinition),
       healthCheckExec_(cfg->healthCheckExec),
+      healthProbe_(cfg->healthProbe),
       startEvent_(cfg->whenEvent),
       startTimeout_(cfg->whenTimeout),
       startsRemain_(cfg->whenStartsLimit),
@@ -701,7 +747,10 @@ void Job::startJobExec() {
 Job::HandleResult Job::onHeartbeatTimerExpired() {
   JobStatus status = getStatus();
   if (status != JobStatus::Maintenance && status != JobStatus::Idle) {
-    if (healthCheckExec_) {
+    if (healthProbe_) {
+      // nothing is spawned, so the spawn backlog does not gate it
+      healthProbe_->run(*loop_, bus_);
+    } else if (healthCheckExec_) {
       if (Spawner::global().overloaded()) {
         // early shed: joining a deep spawn backlog only inflates
         // round trips; skipping now is the same observable as the
@@ -867,6 +916,7 @@ void Job::finishCleanup() {
       regRetryTimer_ = 0;
   if (exec_ && exec_->running()) exec_->term();
   if (healthCheckExec_ && healthCheckExec_->running()) healthCheckExec_->term();
+  if (healthProbe_ && healthProbe_->running()) healthProbe_->cancel();
 
   if (service_) service_->deregister();
   bus_->unsubscribe(this);
