@@ -29,29 +29,24 @@ class ControlServer {
   ControlServer(Loop& loop, std::string socketPath);
   ~ControlServer();
 
-  // Unlink stale socket (control/control.go:61-73), then bind. A failed
-  // bind retries 10x1s on a LOOP TIMER (the reference retries inside a
-  // goroutine, control/control.go:125-140) so event dispatch never
-  // stalls behind a contended socket; after the last failed attempt the
-  // daemon exits fatally like the reference's log.Fatal. Returns false
-  // only for unretryable config errors (missing path, unremovable stale
-  // socket).
+  // Unlink stale socket (control/control.go:61-73), then bind through
+  // http::Server::listenUnixRetrying, which owns the 10x1s retry on a
+  // loop timer and the fatal exit after the last failed attempt. Returns
+  // false only for unretryable config errors (missing path, unremovable
+  // stale socket).
   bool start(std::shared_ptr<Bus> bus, std::string* err);
-  void stop();
+  void stop();  // also unlinks the socket
 
   const std::string& socketPath() const { return socketPath_; }
 
  private:
   http::Response handle(const http::Request& req);
-  bool tryListen(std::string* bindErr);
-  void scheduleRetry(int attempt, const std::string& lastErr);
 
   Loop& loop_;
   std::string socketPath_;
   std::shared_ptr<Bus> bus_;
   std::unique_ptr<http::Server> server_;
   std::shared_ptr<prom::Family> requestCounter_;
-  uint64_t retryTimer_ = 0;
 };
 
 }  // namespace cpilot

@@ -6,6 +6,8 @@
 // keep-alives (control/control.go:110).
 #pragma once
 
+#include <sys/socket.h>
+
 #include <functional>
 #include <map>
 #include <mutex>
@@ -34,6 +36,29 @@ struct Response {
 const char* statusText(int code);
 
 using Handler = std::function<Response(const Request&)>;
+using Headers = std::map<std::string, std::string>;
+
+// ---- message-head parsing: pure functions shared by server and client ----
+
+// Header lines of head[pos, end), where `end` is the offset of the
+// CRLFCRLF that closes the head. Keys are lower-cased, only leading
+// spaces are stripped from values, a repeated key keeps the last value
+// and a line without ':' is skipped.
+void parseHeaderLines(const std::string& head, size_t pos, size_t end,
+                      Headers* out);
+// "METHOD target VERSION": the target lies between the first and the last
+// space and splits at the first '?'. False with fewer than two spaces.
+bool parseRequestLine(const std::string& line, Request* req);
+// Request line plus header lines; `headerEnd` is the offset just past
+// the closing CRLFCRLF.
+bool parseRequestHead(const std::string& buf, size_t headerEnd, Request* req);
+// The integer after the first space of a response that starts with
+// "HTTP/" (0 when it is not a number); -1 for anything else.
+int parseStatus(const std::string& resp);
+// 0 when absent or non-numeric; a negative value wraps to a huge size.
+size_t contentLength(const Headers& headers);
+// Transfer-Encoding contains "chunked" in any letter case.
+bool isChunked(const Headers& headers);
 
 class Server {
  public:
@@ -41,17 +66,31 @@ class Server {
   ~Server();
 
   // Bind + listen on a unix socket path (unlinks nothing; caller manages
-  // stale sockets) or a TCP port. Return false on bind/listen failure.
+  // stale sockets) or a TCP port. Return false on bind/listen failure,
+  // which includes a path too long for sockaddr_un.
   bool listenUnix(const std::string& path, std::string* err);
   bool listenTcp(const std::string& ip, int port, std::string* err);
 
-  void stop();  // close listener and all connections
+  // Run `listen` (listenUnix or listenTcp bound to its address) now and,
+  // while it fails, once a second on a loop timer, never by sleeping on
+  // the reactor; the tenth failed attempt is fatal like the reference's
+  // log.Fatal (control/control.go:125-140, telemetry/telemetry.go:77-91).
+  // onBound runs once the listener is up. `name` prefixes the retry
+  // warning, `addr` is the address as logged, and `attempt` is advanced
+  // by the timer. Return whether this attempt bound.
+  using ListenFn = std::function<bool(std::string* err)>;
+  bool listenRetrying(ListenFn listen, const std::string& name,
+                      const std::string& addr, std::function<void()> onBound,
+                      int attempt = 1);
 
- public:
-  struct Conn;
+  void stop();  // close listener and all connections, drop a pending retry
 
  private:
+  struct Conn;
+  bool bindAndListen(int fd, const struct sockaddr* addr, socklen_t len,
+                     std::string* err);
   void acceptReady();
+  void armDeadline(const std::shared_ptr<Conn>& c);
   void connReadable(std::shared_ptr<Conn> c);
   void connWritable(std::shared_ptr<Conn> c);
   void beginWrite(const std::shared_ptr<Conn>& c, const Response& resp);
@@ -61,6 +100,7 @@ class Server {
   Loop& loop_;
   Handler handler_;
   int listenFd_ = -1;
+  uint64_t retryTimer_ = 0;
   std::map<int, std::shared_ptr<Conn>> conns_;
 };
 
@@ -71,7 +111,7 @@ struct ClientResult {
   int status = 0;
   std::string body;
   std::string error;
-  std::map<std::string, std::string> headers;  // lower-cased keys
+  Headers headers;  // lower-cased keys
 };
 
 // Cancellation for long-polling requests (Consul blocking queries):
@@ -102,7 +142,8 @@ struct TlsOptions {
   bool insecureSkipVerify = false;
 };
 
-// target: "unix:<path>" or "host:port"
+// target: "unix:<path>" or "host:port". A unix path too long for
+// sockaddr_un is an error, never truncated.
 ClientResult request(const std::string& target, const std::string& method,
                      const std::string& path, const std::string& body,
                      const std::string& contentType = "application/json",

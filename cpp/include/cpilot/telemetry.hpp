@@ -71,9 +71,8 @@ class Telemetry {
   void monitorJobs(const std::vector<std::shared_ptr<Job>>& jobs);
   void monitorWatches(const std::vector<std::shared_ptr<Watch>>& watches);
 
-  // Bind, retrying 10x1s on a loop timer (never blocks the reactor);
-  // exits fatally after the last failed attempt like the reference's
-  // listenWithRetry + log.Fatal (telemetry/telemetry.go:77-91).
+  // Bind through http::Server::listenTcpRetrying (10x1s on a loop timer,
+  // fatal after the last failed attempt); always returns true.
   bool start(std::string* err);
   void stop();
 
@@ -82,7 +81,6 @@ class Telemetry {
  private:
   http::Response handle(const http::Request& req);
   std::string statusJson();
-  void scheduleRetry(int attempt, const std::string& lastErr);
 
   Loop& loop_;
   std::shared_ptr<TelemetryConfig> cfg_;
@@ -90,7 +88,6 @@ class Telemetry {
   std::vector<std::shared_ptr<Metric>> metrics_;
   std::vector<std::shared_ptr<Job>> jobs_;
   std::vector<std::string> watchNames_;
-  uint64_t retryTimer_ = 0;
 };
 
 }  // namespace cpilot

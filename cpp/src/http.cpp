@@ -42,6 +42,7 @@ const char* statusText(int code) {
 static constexpr size_t kMaxHeaderBytes = 64 * 1024;
 static constexpr size_t kMaxBodyBytes = 4 * 1024 * 1024;
 static constexpr int kConnDeadlineSecs = 10;
+static constexpr int kListenAttempts = 10;  // one second apart
 
 struct Server::Conn {
   int fd = -1;
@@ -68,20 +69,28 @@ static void setNonblock(int fd) {
   fcntl(fd, F_SETFD, FD_CLOEXEC);
 }
 
-bool Server::listenUnix(const std::string& path, std::string* err) {
-  int fd = socket(AF_UNIX, SOCK_STREAM | SOCK_CLOEXEC, 0);
-  if (fd < 0) {
-    *err = strerror(errno);
+// Fill a unix sockaddr; a path that does not fit is an error, never
+// truncated (the socket would live at a path nobody asked for).
+static bool unixAddr(const std::string& path, struct sockaddr_un* addr,
+                     std::string* err) {
+  memset(addr, 0, sizeof(*addr));
+  addr->sun_family = AF_UNIX;
+  if (path.size() >= sizeof(addr->sun_path)) {
+    *err = "unix socket path too long (" + std::to_string(path.size()) +
+           " bytes, limit " + std::to_string(sizeof(addr->sun_path) - 1) +
+           "): " + path;
     return false;
   }
-  struct sockaddr_un addr;
-  memset(&addr, 0, sizeof(addr));
-  addr.sun_family = AF_UNIX;
-  strncpy(addr.sun_path, path.c_str(), sizeof(addr.sun_path) - 1);
-  if (bind(fd, (struct sockaddr*)&addr, sizeof(addr)) != 0 ||
-      listen(fd, 128) != 0) {
+  memcpy(addr->sun_path, path.data(), path.size());
+  return true;
+}
+
+// takes ownership of fd (which may be -1 from a failed socket())
+bool Server::bindAndListen(int fd, const struct sockaddr* addr, socklen_t len,
+                           std::string* err) {
+  if (fd < 0 || bind(fd, addr, len) != 0 || listen(fd, 128) != 0) {
     *err = strerror(errno);
-    close(fd);
+    if (fd >= 0) close(fd);
     return false;
   }
   setNonblock(fd);
@@ -90,52 +99,67 @@ bool Server::listenUnix(const std::string& path, std::string* err) {
   return true;
 }
 
+bool Server::listenUnix(const std::string& path, std::string* err) {
+  struct sockaddr_un addr;
+  if (!unixAddr(path, &addr, err)) return false;
+  int fd = socket(AF_UNIX, SOCK_STREAM | SOCK_CLOEXEC, 0);
+  return bindAndListen(fd, (struct sockaddr*)&addr, sizeof(addr), err);
+}
+
 bool Server::listenTcp(const std::string& ip, int port, std::string* err) {
-  int fd = socket(AF_INET, SOCK_STREAM | SOCK_CLOEXEC, 0);
-  if (fd < 0) {
-    *err = strerror(errno);
-    return false;
-  }
-  int one = 1;
-  setsockopt(fd, SOL_SOCKET, SO_REUSEADDR, &one, sizeof(one));
   struct sockaddr_in addr;
   memset(&addr, 0, sizeof(addr));
   addr.sin_family = AF_INET;
   addr.sin_port = htons(port);
-  if (ip.empty() || ip == "0.0.0.0") {
+  // empty, 0.0.0.0 and unparseable addresses all mean "any"
+  if (inet_pton(AF_INET, ip.c_str(), &addr.sin_addr) != 1)
     addr.sin_addr.s_addr = INADDR_ANY;
-  } else if (inet_pton(AF_INET, ip.c_str(), &addr.sin_addr) != 1) {
-    addr.sin_addr.s_addr = INADDR_ANY;
+  int fd = socket(AF_INET, SOCK_STREAM | SOCK_CLOEXEC, 0);
+  int one = 1;
+  if (fd >= 0) setsockopt(fd, SOL_SOCKET, SO_REUSEADDR, &one, sizeof(one));
+  return bindAndListen(fd, (struct sockaddr*)&addr, sizeof(addr), err);
+}
+
+bool Server::listenRetrying(ListenFn listen, const std::string& name,
+                            const std::string& addr,
+                            std::function<void()> onBound, int attempt) {
+  std::string err;
+  if (listen(&err)) {
+    onBound();
+    return true;
   }
-  if (bind(fd, (struct sockaddr*)&addr, sizeof(addr)) != 0 ||
-      listen(fd, 128) != 0) {
-    *err = strerror(errno);
-    close(fd);
+  if (attempt == 1)
+    LOG_WARN("%s: error listening at %s: %s (retrying)", name.c_str(),
+             addr.c_str(), err.c_str());
+  if (attempt >= kListenAttempts) {
+    // parity with the reference's log.Fatal after exhausted retries
+    logging::logf(logging::Level::Fatal, "error listening to socket at %s: %s",
+                  addr.c_str(), err.c_str());
     return false;
   }
-  setNonblock(fd);
-  listenFd_ = fd;
-  loop_.watchFd(fd, EPOLLIN, [this](uint32_t) { acceptReady(); });
-  return true;
+  retryTimer_ = loop_.addTimeout(std::chrono::seconds(1), [=] {
+    retryTimer_ = 0;
+    listenRetrying(listen, name, addr, onBound, attempt + 1);
+  });
+  return false;
 }
 
 void Server::stop() {
+  if (retryTimer_) {
+    loop_.cancelTimer(retryTimer_);
+    retryTimer_ = 0;
+  }
   if (listenFd_ >= 0) {
     loop_.unwatchFd(listenFd_);
     close(listenFd_);
     listenFd_ = -1;
   }
-  for (auto& kv : conns_) {
-    // cancel deadline timers: their callbacks capture this server
-    if (kv.second->deadlineTimer) {
-      loop_.cancelTimer(kv.second->deadlineTimer);
-      kv.second->deadlineTimer = 0;
-    }
-    loop_.unwatchFd(kv.first);
-    close(kv.first);
-    kv.second->fd = -1;
+  // closeConn also cancels the deadline timer, whose callback captures
+  // this server
+  while (!conns_.empty()) {
+    std::shared_ptr<Conn> c = conns_.begin()->second;  // outlives the erase
+    closeConn(c);
   }
-  conns_.clear();
 }
 
 void Server::acceptReady() {
@@ -146,23 +170,27 @@ void Server::acceptReady() {
     auto c = std::make_shared<Conn>();
     c->fd = fd;
     conns_[fd] = c;
-    // hard per-connection deadline: a client that dribbles its request
-    // (slow-loris) or refuses to read the response is dropped, freeing
-    // the fd and buffer; reset once when the response starts
-    c->deadlineTimer = loop_.addTimeout(
-        std::chrono::seconds(kConnDeadlineSecs),
-        [this, c] {
-          c->deadlineTimer = 0;
-          closeConn(c);
-        });
-    loop_.watchFd(fd, EPOLLIN | EPOLLHUP, [this, c](uint32_t events) {
+    armDeadline(c);
+    loop_.watchFd(fd, EPOLLIN | EPOLLHUP, [this, c](uint32_t) {
       if (c->writing)
         connWritable(c);
       else
         connReadable(c);
-      (void)events;
     });
   }
+}
+
+// Hard per-connection deadline: a client that dribbles its request
+// (slow-loris) or refuses to read the response is dropped, freeing the
+// fd and buffer. Armed on accept and re-armed once when the response
+// starts.
+void Server::armDeadline(const std::shared_ptr<Conn>& c) {
+  if (c->deadlineTimer) loop_.cancelTimer(c->deadlineTimer);
+  c->deadlineTimer =
+      loop_.addTimeout(std::chrono::seconds(kConnDeadlineSecs), [this, c] {
+        c->deadlineTimer = 0;
+        closeConn(c);
+      });
 }
 
 void Server::closeConn(const std::shared_ptr<Conn>& c) {
@@ -191,14 +219,7 @@ void Server::beginWrite(const std::shared_ptr<Conn>& c,
   c->outbuf = std::move(out);
   c->outoff = 0;
   c->writing = true;
-  // fresh deadline for the write phase
-  if (c->deadlineTimer) loop_.cancelTimer(c->deadlineTimer);
-  c->deadlineTimer = loop_.addTimeout(
-      std::chrono::seconds(kConnDeadlineSecs),
-      [this, c] {
-        c->deadlineTimer = 0;
-        closeConn(c);
-      });
+  armDeadline(c);  // fresh deadline for the write phase
   connWritable(c);
 }
 
@@ -220,8 +241,6 @@ void Server::connWritable(std::shared_ptr<Conn> c) {
   }
   closeConn(c);
 }
-
-static bool parseHeaders(Server::Conn* c);
 
 void Server::connReadable(std::shared_ptr<Conn> c) {
   char buf[8192];
@@ -248,9 +267,7 @@ void Server::connReadable(std::shared_ptr<Conn> c) {
   if (!c->headersDone) {
     size_t end = c->inbuf.find("\r\n\r\n");
     if (end == std::string::npos) {
-      if (c->inbuf.size() > kMaxHeaderBytes) {
-        beginWrite(c, errorResponse(431));
-      }
+      if (c->inbuf.size() > kMaxHeaderBytes) beginWrite(c, errorResponse(431));
       return;  // wait for more (bounded by the connection deadline)
     }
     c->headerEnd = end + 4;
@@ -258,10 +275,11 @@ void Server::connReadable(std::shared_ptr<Conn> c) {
       beginWrite(c, errorResponse(431));
       return;
     }
-    if (!parseHeaders(c.get())) {
+    if (!parseRequestHead(c->inbuf, c->headerEnd, &c->req)) {
       closeConn(c);
       return;
     }
+    c->contentLength = contentLength(c->req.headers);
     c->headersDone = true;
     // no chunked request support: require a length (net/http would
     // dechunk; our endpoints only ever see small bodies)
@@ -287,42 +305,65 @@ Response Server::errorResponse(int status) {
   return resp;
 }
 
-static bool parseHeaders(Server::Conn* c) {
-  const std::string& b = c->inbuf;
-  size_t lineEnd = b.find("\r\n");
-  if (lineEnd == std::string::npos) return false;
-  std::string reqLine = b.substr(0, lineEnd);
-  size_t sp1 = reqLine.find(' ');
-  size_t sp2 = reqLine.rfind(' ');
-  if (sp1 == std::string::npos || sp2 == sp1) return false;
-  c->req.method = reqLine.substr(0, sp1);
-  std::string target = reqLine.substr(sp1 + 1, sp2 - sp1 - 1);
-  size_t q = target.find('?');
-  if (q != std::string::npos) {
-    c->req.path = target.substr(0, q);
-    c->req.query = target.substr(q + 1);
-  } else {
-    c->req.path = target;
-  }
-  size_t pos = lineEnd + 2;
-  while (pos < c->headerEnd - 2) {
-    size_t eol = b.find("\r\n", pos);
-    if (eol == std::string::npos || eol >= c->headerEnd - 2) break;
-    std::string line = b.substr(pos, eol - pos);
+// ---------------- message-head parsing ----------------
+
+static std::string toLower(std::string s) {
+  for (auto& ch : s) ch = (char)tolower((unsigned char)ch);
+  return s;
+}
+
+void parseHeaderLines(const std::string& head, size_t pos, size_t end,
+                      Headers* out) {
+  while (pos < end) {
+    size_t eol = head.find("\r\n", pos);
+    if (eol == std::string::npos || eol > end) break;
+    const char* c = (const char*)memchr(head.data() + pos, ':', eol - pos);
+    if (c) {
+      size_t colon = c - head.data();
+      size_t vstart = colon + 1;
+      while (vstart < eol && head[vstart] == ' ') vstart++;
+      (*out)[toLower(head.substr(pos, colon - pos))] =
+          head.substr(vstart, eol - vstart);
+    }
     pos = eol + 2;
-    size_t colon = line.find(':');
-    if (colon == std::string::npos) continue;
-    std::string key = line.substr(0, colon);
-    for (auto& ch : key) ch = tolower((unsigned char)ch);
-    size_t vstart = colon + 1;
-    while (vstart < line.size() && line[vstart] == ' ') vstart++;
-    c->req.headers[key] = line.substr(vstart);
   }
-  auto it = c->req.headers.find("content-length");
-  c->contentLength = (it != c->req.headers.end())
-                         ? (size_t)atoll(it->second.c_str())
-                         : 0;
+}
+
+bool parseRequestLine(const std::string& line, Request* req) {
+  size_t sp1 = line.find(' ');
+  size_t sp2 = line.rfind(' ');
+  if (sp1 == std::string::npos || sp2 == sp1) return false;
+  req->method = line.substr(0, sp1);
+  std::string target = line.substr(sp1 + 1, sp2 - sp1 - 1);
+  size_t q = target.find('?');
+  req->path = target.substr(0, q);
+  req->query = q == std::string::npos ? "" : target.substr(q + 1);
   return true;
+}
+
+bool parseRequestHead(const std::string& buf, size_t headerEnd, Request* req) {
+  size_t lineEnd = buf.find("\r\n");
+  if (lineEnd == std::string::npos || lineEnd + 4 > headerEnd) return false;
+  if (!parseRequestLine(buf.substr(0, lineEnd), req)) return false;
+  parseHeaderLines(buf, lineEnd + 2, headerEnd - 4, &req->headers);
+  return true;
+}
+
+int parseStatus(const std::string& resp) {
+  if (resp.compare(0, 5, "HTTP/") != 0) return -1;
+  // no space at all: find() gives npos and atoi reads from the start
+  return atoi(resp.c_str() + resp.find(' ') + 1);
+}
+
+size_t contentLength(const Headers& headers) {
+  auto it = headers.find("content-length");
+  return it == headers.end() ? 0 : (size_t)atoll(it->second.c_str());
+}
+
+bool isChunked(const Headers& headers) {
+  auto it = headers.find("transfer-encoding");
+  return it != headers.end() &&
+         toLower(it->second).find("chunked") != std::string::npos;
 }
 
 // ---------------- blocking client ----------------
@@ -351,21 +392,23 @@ bool CancelToken::cancelled() {
 
 namespace {
 
-int connectTarget(const std::string& target, int timeoutMs, std::string* err) {
+void setIoTimeout(int fd, int timeoutMs) {
+  struct timeval tv;
+  tv.tv_sec = timeoutMs / 1000;
+  tv.tv_usec = (timeoutMs % 1000) * 1000;
+  setsockopt(fd, SOL_SOCKET, SO_RCVTIMEO, &tv, sizeof(tv));
+  setsockopt(fd, SOL_SOCKET, SO_SNDTIMEO, &tv, sizeof(tv));
+}
+
+int connectTarget(const std::string& target, std::string* err) {
   int fd = -1;
   if (target.rfind("unix:", 0) == 0) {
-    fd = socket(AF_UNIX, SOCK_STREAM | SOCK_CLOEXEC, 0);
-    if (fd < 0) {
-      *err = strerror(errno);
-      return -1;
-    }
     struct sockaddr_un addr;
-    memset(&addr, 0, sizeof(addr));
-    addr.sun_family = AF_UNIX;
-    strncpy(addr.sun_path, target.c_str() + 5, sizeof(addr.sun_path) - 1);
-    if (connect(fd, (struct sockaddr*)&addr, sizeof(addr)) != 0) {
+    if (!unixAddr(target.substr(5), &addr, err)) return -1;
+    fd = socket(AF_UNIX, SOCK_STREAM | SOCK_CLOEXEC, 0);
+    if (fd < 0 || connect(fd, (struct sockaddr*)&addr, sizeof(addr)) != 0) {
       *err = strerror(errno);
-      close(fd);
+      if (fd >= 0) close(fd);
       return -1;
     }
   } else {
@@ -395,22 +438,10 @@ int connectTarget(const std::string& target, int timeoutMs, std::string* err) {
       fd = -1;
     }
     freeaddrinfo(res);
-    if (fd < 0) {
-      *err = "connection refused";
-      return -1;
-    }
+    if (fd < 0) *err = "connection refused";
   }
-  struct timeval tv;
-  tv.tv_sec = timeoutMs / 1000;
-  tv.tv_usec = (timeoutMs % 1000) * 1000;
-  setsockopt(fd, SOL_SOCKET, SO_RCVTIMEO, &tv, sizeof(tv));
-  setsockopt(fd, SOL_SOCKET, SO_SNDTIMEO, &tv, sizeof(tv));
   return fd;
 }
-
-}  // namespace
-
-namespace {
 
 // thin transport abstraction so the request logic is shared between
 // plain sockets and TLS sessions
@@ -481,10 +512,6 @@ struct Transport {
   }
 };
 
-}  // namespace
-
-namespace {
-
 // Thread-local keep-alive pool: one cached plain-TCP/unix connection
 // per target, giving the same connection reuse the reference's consul
 // client inherits from Go's http.Transport. Plain + uncancellable
@@ -510,13 +537,9 @@ int poolTake(const std::string& target) {
 }
 
 void poolStore(const std::string& target, int fd) {
-  auto it = connPool.conns.find(target);
-  if (it != connPool.conns.end()) {
-    close(it->second);
-    it->second = fd;
-  } else {
-    connPool.conns[target] = fd;
-  }
+  int& slot = connPool.conns.emplace(target, -1).first->second;
+  if (slot >= 0) close(slot);
+  slot = fd;
 }
 
 // incremental chunked-body decoder: returns true once the terminal
@@ -536,6 +559,112 @@ bool tryDechunk(const std::string& data, std::string* out) {
   }
 }
 
+// A pooled connection when allowed and available, else a fresh one;
+// either way it carries this request's timeouts (a pooled fd still has
+// the previous request's).
+int acquireConn(const std::string& target, int timeoutMs, bool usePool,
+                bool* fromPool, std::string* err) {
+  int fd = usePool ? poolTake(target) : -1;
+  *fromPool = fd >= 0;
+  if (fd < 0) fd = connectTarget(target, err);
+  if (fd >= 0) setIoTimeout(fd, timeoutMs);
+  return fd;
+}
+
+std::string serialiseRequest(const std::string& method, const std::string& path,
+                             const std::string& host, bool keepAlive,
+                             const Headers& headers, const std::string& body,
+                             const std::string& contentType) {
+  std::string req = method + " " + path + " HTTP/1.1\r\n";
+  req += "Host: " + host + "\r\n";
+  req += keepAlive ? "Connection: keep-alive\r\n" : "Connection: close\r\n";
+  for (auto& kv : headers) req += kv.first + ": " + kv.second + "\r\n";
+  if (!body.empty() || method == "POST" || method == "PUT") {
+    req += "Content-Type: " + contentType + "\r\n";
+    req += "Content-Length: " + std::to_string(body.size()) + "\r\n";
+  }
+  req += "\r\n";
+  req += body;
+  return req;
+}
+
+bool writeAll(Transport& t, const std::string& data) {
+  size_t off = 0;
+  while (off < data.size()) {
+    ssize_t n = t.send(data.data() + off, data.size() - off);
+    if (n > 0)
+      off += n;
+    else if (!(n < 0 && errno == EINTR && !t.ssl))
+      return false;
+  }
+  return true;
+}
+
+// false on EOF or error/timeout
+bool readMore(Transport& t, std::string* resp) {
+  char buf[8192];
+  while (true) {
+    ssize_t n = t.recv(buf, sizeof(buf));
+    if (n > 0) {
+      resp->append(buf, n);
+      return true;
+    }
+    if (!(n < 0 && errno == EINTR && !t.ssl)) return false;
+  }
+}
+
+enum class ReadResult { Ok, Empty, Malformed, Truncated };
+
+// Read incrementally: the head first, then exactly the framed body.
+// Fills status, headers and body; *bodyFramed is false when the body
+// ran to EOF, which leaves the connection unusable.
+ReadResult readResponse(Transport& t, ClientResult* result, bool* bodyFramed) {
+  std::string resp;
+  size_t headerEnd;
+  while ((headerEnd = resp.find("\r\n\r\n")) == std::string::npos) {
+    if (!readMore(t, &resp)) break;
+  }
+  if (resp.empty()) return ReadResult::Empty;
+  int status = parseStatus(resp);
+  if (headerEnd == std::string::npos || status < 0)
+    return ReadResult::Malformed;
+  result->status = status;
+  parseHeaderLines(resp, resp.find("\r\n") + 2, headerEnd, &result->headers);
+
+  const size_t bodyStart = headerEnd + 4;
+  *bodyFramed = true;
+  if (isChunked(result->headers)) {
+    // timeout/EOF mid-body: a truncated framed body is an error, not a
+    // short success (Go's client errors the same way)
+    std::string decoded;
+    while (!tryDechunk(resp.substr(bodyStart), &decoded)) {
+      if (!readMore(t, &resp)) return ReadResult::Truncated;
+    }
+    result->body = std::move(decoded);
+  } else if (result->headers.count("content-length")) {
+    size_t want = contentLength(result->headers);
+    while (resp.size() < bodyStart + want) {
+      if (!readMore(t, &resp)) return ReadResult::Truncated;
+    }
+    result->body = resp.substr(bodyStart, want);
+  } else {
+    // no framing: read to EOF, connection not reusable
+    while (readMore(t, &resp)) {
+    }
+    result->body = resp.substr(bodyStart);
+    *bodyFramed = false;
+  }
+  return ReadResult::Ok;
+}
+
+// reuse only when the server did not ask to close and sent a real status
+bool serverKeepsAlive(const ClientResult& result) {
+  auto it = result.headers.find("connection");
+  bool closes = it != result.headers.end() &&
+                toLower(it->second).find("close") != std::string::npos;
+  return !closes && result.status > 0;
+}
+
 }  // namespace
 
 ClientResult request(const std::string& target, const std::string& method,
@@ -550,28 +679,23 @@ ClientResult request(const std::string& target, const std::string& method,
     return result;
   }
   const bool tlsOn = tls && tls->enabled;
+  // pooling applies to plain, uncancellable requests only
   const bool reusable = !tlsOn && cancel == nullptr;
+  const std::string host =
+      target.rfind("unix:", 0) == 0 ? "localhost" : target;
+  const std::string req = serialiseRequest(method, path, host, reusable,
+                                           headers, body, contentType);
 
+  // A pooled connection may have gone stale while idle, which shows as a
+  // failed write or an empty read; only then is there a second attempt,
+  // always on a fresh connection.
   for (int attempt = 0; attempt < 2; attempt++) {
     result = ClientResult{};
     Transport t;
     bool fromPool = false;
-    if (reusable && attempt == 0) {
-      t.fd = poolTake(target);
-      fromPool = t.fd >= 0;
-    }
-    if (t.fd < 0) {
-      t.fd = connectTarget(target, timeoutMs, &result.error);
-      if (t.fd < 0) return result;
-    } else {
-      // refresh the timeouts: the pooled fd carries the previous
-      // request's deadline settings
-      struct timeval tv;
-      tv.tv_sec = timeoutMs / 1000;
-      tv.tv_usec = (timeoutMs % 1000) * 1000;
-      setsockopt(t.fd, SOL_SOCKET, SO_RCVTIMEO, &tv, sizeof(tv));
-      setsockopt(t.fd, SOL_SOCKET, SO_SNDTIMEO, &tv, sizeof(tv));
-    }
+    t.fd = acquireConn(target, timeoutMs, reusable && attempt == 0, &fromPool,
+                       &result.error);
+    if (t.fd < 0) return result;
     struct Disarm {
       CancelToken* ct;
       ~Disarm() {
@@ -579,137 +703,29 @@ ClientResult request(const std::string& target, const std::string& method,
       }
     } disarm{cancel};
     if (cancel) cancel->arm(t.fd);
+    if (tlsOn && !t.startTls(host, *tls, &result.error)) return result;
 
-    std::string host = target.rfind("unix:", 0) == 0 ? "localhost" : target;
-    if (tlsOn) {
-      if (!t.startTls(host, *tls, &result.error)) return result;
+    if (!writeAll(t, req)) {
+      if (fromPool) continue;  // retry case 1: stale keep-alive
+      break;                   // "write failed"
     }
-
-    std::string req = method + " " + path + " HTTP/1.1\r\n";
-    req += "Host: " + host + "\r\n";
-    req += reusable ? "Connection: keep-alive\r\n" : "Connection: close\r\n";
-    for (auto& kv : headers) req += kv.first + ": " + kv.second + "\r\n";
-    if (!body.empty() || method == "POST" || method == "PUT") {
-      req += "Content-Type: " + contentType + "\r\n";
-      req += "Content-Length: " + std::to_string(body.size()) + "\r\n";
-    }
-    req += "\r\n";
-    req += body;
-
-    bool ioFailed = false;
-    size_t off = 0;
-    while (off < req.size()) {
-      ssize_t n = t.send(req.data() + off, req.size() - off);
-      if (n <= 0) {
-        if (n < 0 && errno == EINTR && !t.ssl) continue;
-        ioFailed = true;
-        break;
-      }
-      off += n;
-    }
-    if (ioFailed) {
-      if (fromPool) continue;  // stale keep-alive: retry on a fresh conn
-      result.error = "write failed";
-      return result;
-    }
-
-    // read incrementally: headers first, then exactly the framed body
-    std::string resp;
-    char buf[8192];
-    size_t headerEnd = std::string::npos;
-    auto readMore = [&]() -> bool {
-      while (true) {
-        ssize_t n = t.recv(buf, sizeof(buf));
-        if (n > 0) {
-          resp.append(buf, n);
-          return true;
-        }
-        if (n < 0 && errno == EINTR && !t.ssl) continue;
-        return false;  // EOF or error/timeout
-      }
-    };
-    bool eof = false;
-    while ((headerEnd = resp.find("\r\n\r\n")) == std::string::npos) {
-      if (!readMore()) {
-        eof = true;
-        break;
-      }
-    }
-    if (headerEnd == std::string::npos || resp.compare(0, 5, "HTTP/") != 0) {
-      if (fromPool && resp.empty()) continue;  // server closed the idle conn
+    bool bodyFramed = false;
+    ReadResult rr = readResponse(t, &result, &bodyFramed);
+    if (rr == ReadResult::Empty && fromPool)
+      continue;  // retry case 2: the server closed the idle connection
+    if (rr == ReadResult::Empty || rr == ReadResult::Malformed) {
       result.error = (cancel && cancel->cancelled()) ? "cancelled"
                                                      : "malformed response";
       return result;
     }
-
-    size_t sp = resp.find(' ');
-    result.status = atoi(resp.c_str() + sp + 1);
-    // response headers (lower-cased keys)
-    size_t pos = resp.find("\r\n") + 2;
-    while (pos < headerEnd) {
-      size_t eol = resp.find("\r\n", pos);
-      if (eol == std::string::npos || eol > headerEnd) break;
-      std::string line = resp.substr(pos, eol - pos);
-      pos = eol + 2;
-      size_t colon = line.find(':');
-      if (colon == std::string::npos) continue;
-      std::string key = line.substr(0, colon);
-      for (auto& ch : key) ch = (char)tolower((unsigned char)ch);
-      size_t vstart = colon + 1;
-      while (vstart < line.size() && line[vstart] == ' ') vstart++;
-      result.headers[key] = line.substr(vstart);
+    if (rr == ReadResult::Truncated) {
+      result.error = "truncated response body";
+      return result;
     }
-
-    auto lower = [](std::string v) {
-      for (auto& ch : v) ch = (char)tolower((unsigned char)ch);
-      return v;
-    };
-    bool chunked = false;
-    auto te = result.headers.find("transfer-encoding");
-    if (te != result.headers.end() &&
-        lower(te->second).find("chunked") != std::string::npos)
-      chunked = true;
-    bool bodyFramed = true;
-    if (chunked) {
-      std::string decoded;
-      while (!tryDechunk(resp.substr(headerEnd + 4), &decoded)) {
-        if (eof || !readMore()) {
-          // timeout/EOF mid-body: a truncated framed body is an error,
-          // not a short success (Go's client errors the same way)
-          result.error = "truncated response body";
-          return result;
-        }
-      }
-      result.body = decoded;
-    } else if (result.headers.count("content-length")) {
-      size_t want =
-          (size_t)atoll(result.headers["content-length"].c_str());
-      while (resp.size() < headerEnd + 4 + want) {
-        if (eof || !readMore()) {
-          result.error = "truncated response body";
-          return result;
-        }
-      }
-      result.body = resp.substr(headerEnd + 4, want);
-    } else {
-      // no framing: read to EOF, connection not reusable
-      while (readMore()) {
-      }
-      result.body = resp.substr(headerEnd + 4);
-      bodyFramed = false;
-    }
-
     result.ok = true;
-    // reuse only when both sides agreed and the body was fully framed
-    bool serverKeeps = true;
-    auto ch = result.headers.find("connection");
-    if (ch != result.headers.end() &&
-        lower(ch->second).find("close") != std::string::npos)
-      serverKeeps = false;
-    if (reusable && bodyFramed && serverKeeps && result.status > 0) {
-      int fd = t.fd;
+    if (reusable && bodyFramed && serverKeepsAlive(result)) {
+      poolStore(target, t.fd);
       t.fd = -1;  // keep it out of Transport's destructor
-      poolStore(target, fd);
     }
     return result;
   }

@@ -20,6 +20,8 @@
 #include <signal.h>
 #include <sys/epoll.h>
 #include <sys/signalfd.h>
+#include <sys/socket.h>
+#include <sys/un.h>
 #include <unistd.h>
 
 #include "cpilot/command.hpp"
@@ -928,6 +930,282 @@ static void testHttpClientFraming() {
   }
 }
 
+// ---- HTTP message-head parsing (pure functions, http.hpp) ----
+
+namespace {
+
+// parse a whole request head the way the server does: the head ends just
+// past the first blank line
+bool parseHead(const std::string& raw, http::Request* req) {
+  size_t end = raw.find("\r\n\r\n");
+  if (end == std::string::npos) return false;
+  return http::parseRequestHead(raw, end + 4, req);
+}
+
+// header lines alone, bracketed like a message head
+http::Headers parseLines(const std::string& lines) {
+  std::string head = "X\r\n" + lines + "\r\n";
+  http::Headers h;
+  http::parseHeaderLines(head, 3, head.size() - 4, &h);
+  return h;
+}
+
+}  // namespace
+
+static void testHttpHeadParsing() {
+  const size_t kBodyCap = 4 * 1024 * 1024;
+  {
+    http::Request req;
+    CHECK(parseHead("POST /v3/metric?x=1&y=2 HTTP/1.1\r\nHost: a\r\n"
+                    "Content-Length: 3\r\n\r\nabc",
+                    &req));
+    CHECK_EQ(req.method, std::string("POST"));
+    CHECK_EQ(req.path, std::string("/v3/metric"));
+    CHECK_EQ(req.query, std::string("x=1&y=2"));
+    CHECK_EQ(req.headers.size(), (size_t)2);
+    CHECK_EQ(req.headers["host"], std::string("a"));
+    CHECK_EQ(http::contentLength(req.headers), (size_t)3);
+  }
+  {
+    // the target lies between the first and the last space
+    http::Request req;
+    CHECK(http::parseRequestLine("GET /a b HTTP/1.1", &req));
+    CHECK_EQ(req.method, std::string("GET"));
+    CHECK_EQ(req.path, std::string("/a b"));
+    CHECK_EQ(req.query, std::string(""));
+  }
+  {
+    http::Request req;
+    CHECK(!http::parseRequestLine("GET /x", &req));  // one space
+    CHECK(!http::parseRequestLine("GET", &req));
+    CHECK(!parseHead("GET /x\r\n\r\n", &req));
+  }
+  {
+    http::Request req;
+    CHECK(parseHead("GET / HTTP/1.1\r\n\r\n", &req));
+    CHECK_EQ(req.path, std::string("/"));
+    CHECK(req.headers.empty());
+    CHECK_EQ(http::contentLength(req.headers), (size_t)0);
+  }
+  // only leading spaces are stripped; tabs and trailing blanks stay
+  CHECK_EQ(parseLines("X-A:   v  \r\n")["x-a"], std::string("v  "));
+  CHECK_EQ(parseLines("X-B:\tv\r\n")["x-b"], std::string("\tv"));
+  {
+    // a line without a colon is skipped and later lines still parse
+    auto h = parseLines("A: 1\r\ngarbage\r\nB: 2\r\n");
+    CHECK_EQ(h.size(), (size_t)2);
+    CHECK_EQ(h["a"], std::string("1"));
+    CHECK_EQ(h["b"], std::string("2"));
+  }
+  {
+    auto h = parseLines("K: 1\r\nk: 2\r\n");  // the last duplicate wins
+    CHECK_EQ(h.size(), (size_t)1);
+    CHECK_EQ(h["k"], std::string("2"));
+  }
+  CHECK_EQ(http::contentLength(parseLines("CONTENT-length: 7\r\n")), (size_t)7);
+  CHECK_EQ(http::contentLength(parseLines("Content-Length: abc\r\n")),
+           (size_t)0);
+  // a negative length wraps far above the body cap (answered 413)
+  CHECK(http::contentLength(parseLines("Content-Length: -1\r\n")) > kBodyCap);
+  // nothing past the end offset is read as a header
+  {
+    std::string head = "X\r\nA: 1\r\n\r\nB: 2\r\n\r\n";
+    http::Headers h;
+    http::parseHeaderLines(head, 3, head.find("\r\n\r\n"), &h);
+    CHECK_EQ(h.size(), (size_t)1);
+  }
+
+  // client status line
+  CHECK_EQ(http::parseStatus("HTTP/1.1 204 No Content\r\n\r\n"), 204);
+  CHECK_EQ(http::parseStatus("HTTP/1.1 abc\r\n\r\n"), 0);
+  CHECK_EQ(http::parseStatus("HTTP/1.1"), 0);
+  CHECK_EQ(http::parseStatus("ICY 200 OK\r\n\r\n"), -1);
+  CHECK_EQ(http::parseStatus(""), -1);
+
+  // client chunked detection: any letter case, substring match
+  CHECK(http::isChunked(parseLines("Transfer-Encoding: CHUNKED\r\n")));
+  CHECK(http::isChunked(parseLines("transfer-encoding: gzip, chunked\r\n")));
+  CHECK(!http::isChunked(parseLines("Transfer-Encoding: gzip\r\n")));
+  CHECK(!http::isChunked(parseLines("Content-Length: 3\r\n")));
+}
+
+// ---- HTTP server + client in one process (http.cpp) ----
+
+namespace {
+
+std::string makeTempDir() {
+  char tmpl[] = "/tmp/cpilot-http-XXXXXX";
+  const char* dir = mkdtemp(tmpl);
+  CHECK(dir != nullptr);
+  return dir ? dir : "";
+}
+
+// a listening blocker on 127.0.0.1:<port> (0 picks a free one); while it
+// is open nobody else can bind the port
+int listenBlocker(int* port) {
+  int fd = socket(AF_INET, SOCK_STREAM, 0);
+  struct sockaddr_in addr;
+  memset(&addr, 0, sizeof(addr));
+  addr.sin_family = AF_INET;
+  addr.sin_addr.s_addr = htonl(INADDR_LOOPBACK);
+  addr.sin_port = htons(*port);
+  CHECK(bind(fd, (struct sockaddr*)&addr, sizeof(addr)) == 0);
+  CHECK(listen(fd, 8) == 0);
+  socklen_t len = sizeof(addr);
+  getsockname(fd, (struct sockaddr*)&addr, &len);
+  *port = ntohs(addr.sin_port);
+  return fd;
+}
+
+}  // namespace
+
+static void testHttpServerRoundTrip() {
+  std::string dir = makeTempDir();
+  std::string path = dir + "/s.sock";
+  Loop loop;
+  http::Server server(loop, [](const http::Request& req) {
+    http::Response resp;
+    if (req.path == "/missing") {
+      resp.status = 404;
+      resp.body = "nope\n";
+      return resp;
+    }
+    resp.body = req.method + "|" + req.path + "|" + req.query + "|" + req.body;
+    return resp;
+  });
+  std::string err;
+  CHECK(server.listenUnix(path, &err));
+  CHECK_EQ(err, std::string(""));
+
+  http::ClientResult post, get, missing;
+  ssize_t rawBytes = -1;
+  std::thread client([&] {
+    std::string target = "unix:" + path;
+    post = http::request(target, "POST", "/p?q=1", "body");
+    get = http::request(target, "GET", "/g", "");
+    missing = http::request(target, "GET", "/missing", "");
+    // a request line with one space: closed without a response
+    int fd = socket(AF_UNIX, SOCK_STREAM, 0);
+    struct sockaddr_un addr;
+    memset(&addr, 0, sizeof(addr));
+    addr.sun_family = AF_UNIX;
+    memcpy(addr.sun_path, path.data(), path.size());
+    CHECK(connect(fd, (struct sockaddr*)&addr, sizeof(addr)) == 0);
+    const char raw[] = "GET /x\r\n\r\n";
+    CHECK_EQ(write(fd, raw, sizeof(raw) - 1), (ssize_t)(sizeof(raw) - 1));
+    struct timeval tv{3, 0};  // a server that never closes fails, not hangs
+    setsockopt(fd, SOL_SOCKET, SO_RCVTIMEO, &tv, sizeof(tv));
+    char buf[64];
+    rawBytes = read(fd, buf, sizeof(buf));
+    close(fd);
+    loop.post([&loop] { loop.stop(); });
+  });
+  loop.run();
+  client.join();
+  server.stop();
+
+  CHECK(post.ok);
+  CHECK_EQ(post.status, 200);
+  CHECK_EQ(post.body, std::string("POST|/p|q=1|body"));
+  CHECK(get.ok);
+  CHECK_EQ(get.status, 200);
+  CHECK_EQ(get.body, std::string("GET|/g||"));
+  CHECK(missing.ok);
+  CHECK_EQ(missing.status, 404);
+  CHECK_EQ(missing.body, std::string("nope\n"));
+  CHECK_EQ(rawBytes, (ssize_t)0);  // EOF, zero response bytes
+
+  unlink(path.c_str());
+  rmdir(dir.c_str());
+}
+
+static void testHttpServerBindRetry() {
+  auto noop = [](const http::Request&) { return http::Response{}; };
+  // the port is taken at first: the server reports not bound, binds on a
+  // retry once the port is free, and then serves
+  {
+    int port = 0;
+    int blocker = listenBlocker(&port);
+    Loop loop;
+    http::Server server(loop, noop);
+    int bound = 0;
+    auto listen = [&](std::string* e) {
+      return server.listenTcp("127.0.0.1", port, e);
+    };
+    CHECK(!server.listenRetrying(listen, "test",
+                                 "127.0.0.1:" + std::to_string(port),
+                                 [&] { bound++; }));
+    CHECK_EQ(bound, 0);
+    close(blocker);
+
+    http::ClientResult r;
+    auto start = Clock::now();
+    std::thread client([&] {
+      std::string target = "127.0.0.1:" + std::to_string(port);
+      while (Clock::now() - start < std::chrono::seconds(3)) {
+        r = http::request(target, "GET", "/", "");
+        if (r.ok) break;
+        usleep(50 * 1000);
+      }
+      loop.post([&loop] { loop.stop(); });
+    });
+    loop.run();
+    client.join();
+    CHECK(r.ok);
+    CHECK_EQ(r.status, 200);
+    CHECK_EQ(bound, 1);
+    CHECK(Clock::now() - start < std::chrono::seconds(3));
+    server.stop();
+  }
+  // stop() while the retry is pending: nothing fires afterwards
+  {
+    int port = 0;
+    int blocker = listenBlocker(&port);
+    Loop loop;
+    http::Server server(loop, noop);
+    int attempts = 0, bound = 0;
+    auto listen = [&](std::string* e) {
+      attempts++;
+      return server.listenTcp("127.0.0.1", port, e);
+    };
+    CHECK(!server.listenRetrying(listen, "test",
+                                 "127.0.0.1:" + std::to_string(port),
+                                 [&] { bound++; }));
+    CHECK_EQ(attempts, 1);
+    server.stop();
+    close(blocker);  // a retry that still fired would now bind
+    loop.addTimeout(std::chrono::milliseconds(1500), [&loop] { loop.stop(); });
+    loop.run();
+    CHECK_EQ(attempts, 1);
+    CHECK_EQ(bound, 0);
+    int again = listenBlocker(&port);  // the port is really free
+    close(again);
+  }
+}
+
+static void testUnixPathTooLong() {
+  std::string dir = makeTempDir();
+  std::string path = dir + "/" + std::string(200 - dir.size() - 1, 'p');
+  CHECK_EQ(path.size(), (size_t)200);
+  Loop loop;
+  http::Server server(
+      loop, [](const http::Request&) { return http::Response{}; });
+  std::string err;
+  CHECK(!server.listenUnix(path, &err));
+  CHECK(err.find("too long") != std::string::npos);
+  CHECK(err.find(path) != std::string::npos);
+
+  auto r = http::request("unix:" + path, "GET", "/", "");
+  CHECK(!r.ok);
+  CHECK(r.error.find("too long") != std::string::npos);
+
+  // neither the path nor its truncation to sun_path's size was created
+  CHECK(access(path.c_str(), F_OK) != 0);
+  struct sockaddr_un addr;
+  CHECK(access(path.substr(0, sizeof(addr.sun_path) - 1).c_str(), F_OK) != 0);
+  CHECK_EQ(rmdir(dir.c_str()), 0);  // so the directory is still empty
+}
+
 int main() {
   testJson5();
   testDurations();
@@ -948,6 +1226,10 @@ int main() {
   testSignalJobMatrix();
   testStartTimeoutQuitsJob();
   testHttpClientFraming();
+  testHttpHeadParsing();
+  testHttpServerRoundTrip();
+  testHttpServerBindRetry();
+  testUnixPathTooLong();
   if (failures) {
     fprintf(stderr, "%d failures\n", failures);
     return 1;
