@@ -35,6 +35,11 @@ def _load():
         _lib.cp_consul_endpoint.restype = ctypes.c_void_p
         _lib.cp_consul_endpoint.argtypes = [
             ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
+        _lib.cp_watch_render.restype = ctypes.c_void_p
+        _lib.cp_watch_render.argtypes = [
+            ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
+            ctypes.c_char_p, ctypes.c_char_p,
+            ctypes.POINTER(ctypes.c_void_p)]
         _lib.cp_free.argtypes = [ctypes.c_void_p]
     return _lib
 
@@ -92,6 +97,20 @@ def consul_endpoint(consul_json):
     lib = _load()
     err = ctypes.c_void_p()
     out = lib.cp_consul_endpoint(consul_json.encode(), ctypes.byref(err))
+    if not out:
+        raise ValueError(_take_string(lib, err.value))
+    return _take_string(lib, out)
+
+
+def watch_render(template_text, health_body_json, name, tag="", dc=""):
+    """Dry-run of a watch's `render`: what the daemon would write for the
+    raw /v1/health/service response body `health_body_json` of service
+    `name`. Raises ValueError on a bad body or a template error."""
+    lib = _load()
+    err = ctypes.c_void_p()
+    out = lib.cp_watch_render(template_text.encode(),
+                              health_body_json.encode(), name.encode(),
+                              tag.encode(), dc.encode(), ctypes.byref(err))
     if not out:
         raise ValueError(_take_string(lib, err.value))
     return _take_string(lib, out)

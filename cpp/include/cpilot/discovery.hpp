@@ -27,7 +27,16 @@ struct ServiceEntry {
   std::string id;
   std::string address;
   int port = 0;
+  // carried for watch templates only; change detection ignores them
+  std::vector<std::string> tags;
+  std::string node;         // Node.Node
+  std::string nodeAddress;  // Node.Address
 };
+
+// Decode a /v1/health/service response body. Entries without a Service
+// object are skipped; a body that does not parse clears *ok.
+std::vector<ServiceEntry> parseHealthEntries(const std::string& body,
+                                             bool* ok);
 
 class ConsulBackend {
  public:

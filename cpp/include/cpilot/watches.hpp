@@ -4,6 +4,8 @@
 // Parity: /root/reference/watches/{watches,config}.go.
 #pragma once
 
+#include <sys/types.h>
+
 #include <memory>
 #include <string>
 #include <vector>
@@ -11,8 +13,19 @@
 #include "cpilot/discovery.hpp"
 #include "cpilot/events.hpp"
 #include "cpilot/json.hpp"
+#include "cpilot/tmpl.hpp"
 
 namespace cpilot {
+
+// extension: `render` writes the watch's healthy set through a template
+// file into `dest` before the change events are published, so an onChange
+// job always finds the file for the set its event is about.
+struct RenderConfig {
+  std::string source;  // template file, absolute
+  std::string dest;    // output file, absolute
+  mode_t mode = 0644;
+  Template tmpl;       // parsed by loadRenderTemplate, not by the decoder
+};
 
 struct WatchConfig {
   std::string name;         // "watch.<service>"
@@ -25,11 +38,31 @@ struct WatchConfig {
   // the poll interval, and idle traffic drops to one request per wait
   // window. `interval` becomes the error-backoff period.
   bool blocking = false;
+  std::shared_ptr<RenderConfig> render;  // null when not configured
 };
 
+// Decodes and validates shape only; never touches the filesystem.
 bool newWatchConfigs(const Json& rawWatches,
                      std::vector<std::shared_ptr<WatchConfig>>* out,
                      std::string* err);
+
+// Read and parse cfg.render->source (no-op without render). On failure
+// sets err to "watch[<name>].render.source: <reason>".
+bool loadRenderTemplate(WatchConfig& cfg, std::string* err);
+
+// What a render template sees as ".": Name/Tag/DC as configured, Healthy,
+// and Services sorted by (Address, Port, ID). An empty Service.Address
+// falls back to Node.Address.
+Json buildRenderData(const std::string& serviceName, const std::string& tag,
+                     const std::string& dc,
+                     const std::vector<ServiceEntry>& entries);
+
+// Make `dest` hold exactly `bytes`: untouched when it already does, else
+// a temporary file in dest's directory with `mode`, renamed over dest.
+// No fsync. On failure returns false, removes the temporary file and
+// leaves dest as it was.
+bool writeFileAtomic(const std::string& dest, const std::string& bytes,
+                     mode_t mode, std::string* err);
 
 class Watch : public std::enable_shared_from_this<Watch> {
  public:
@@ -39,7 +72,8 @@ class Watch : public std::enable_shared_from_this<Watch> {
         tag_(cfg->tag),
         dc_(cfg->dc),
         poll_(cfg->poll),
-        blocking_(cfg->blocking) {}
+        blocking_(cfg->blocking),
+        render_(cfg->render) {}
 
   const std::string& name() const { return name_; }
   const std::string& serviceName() const { return serviceName_; }
@@ -51,10 +85,13 @@ class Watch : public std::enable_shared_from_this<Watch> {
   void tick();
   void issueBlocking();
   void onResult(bool ok, std::vector<ServiceEntry> entries);
+  bool renderDest(const std::vector<ServiceEntry>& entries, std::string* err);
 
   std::string name_, serviceName_, tag_, dc_;
   int poll_;
   bool blocking_ = false;
+  std::shared_ptr<RenderConfig> render_;
+  bool rendered_ = false;  // first successful result seen this generation
   uint64_t lastIndex_ = 0;
   Loop* loop_ = nullptr;
   std::shared_ptr<Bus> bus_;

@@ -139,7 +139,13 @@ std::unique_ptr<AppConfig> loadConfig(const std::string& path,
   if (!readFile(path, &data, err)) return nullptr;
   std::string rendered;
   if (!renderString(data, &rendered, err)) return nullptr;
-  return newConfig(rendered, err);
+  auto cfg = newConfig(rendered, err);
+  if (!cfg) return nullptr;
+  // newConfig stays filesystem-free; the daemon's path reads and parses
+  // each watch's render template here, at start and on every reload
+  for (auto& watch : cfg->watches)
+    if (!loadRenderTemplate(*watch, err)) return nullptr;
+  return cfg;
 }
 
 bool renderConfigFile(const std::string& configPath,

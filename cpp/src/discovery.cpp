@@ -335,8 +335,6 @@ void ConsulBackend::serviceDeregister(const std::string& id, DoneCb cb) {
   if (!accepted) loop_->post([cb] { cb(false, "queue full"); });
 }
 
-namespace {
-
 std::vector<ServiceEntry> parseHealthEntries(const std::string& body,
                                              bool* ok) {
   std::vector<ServiceEntry> entries;
@@ -353,6 +351,16 @@ std::vector<ServiceEntry> parseHealthEntries(const std::string& body,
           if (v->isString()) entry.address = v->str();
         if (const Json* v = svc->find("Port"))
           if (v->isNumber()) entry.port = (int)v->asInt();
+        if (const Json* v = svc->find("Tags"))
+          if (v->isArray())
+            for (auto& t : v->array())
+              if (t.isString()) entry.tags.push_back(t.str());
+        if (const Json* node = e.find("Node")) {
+          if (const Json* v = node->find("Node"))
+            if (v->isString()) entry.node = v->str();
+          if (const Json* v = node->find("Address"))
+            if (v->isString()) entry.nodeAddress = v->str();
+        }
         entries.push_back(std::move(entry));
       }
     }
@@ -361,8 +369,6 @@ std::vector<ServiceEntry> parseHealthEntries(const std::string& body,
   }
   return entries;
 }
-
-}  // namespace
 
 void ConsulBackend::healthService(const std::string& name,
                                   const std::string& tag,

@@ -12,6 +12,7 @@
 #include "cpilot/timing.hpp"
 #include "cpilot/tmpl.hpp"
 #include "cpilot/version.hpp"
+#include "cpilot/watches.hpp"
 
 using namespace cpilot;
 
@@ -87,6 +88,29 @@ char* cp_consul_endpoint(const char* consulJson, char** errOut) {
       return nullptr;
     }
     return dupString(backend->scheme() + "://" + backend->address());
+  } catch (const std::exception& e) {
+    if (errOut) *errOut = dupString(e.what());
+    return nullptr;
+  }
+}
+
+// Dry-run of a watch's `render`: parse a raw /v1/health/service response
+// body the way the daemon does, build the watch data model for service
+// `name` (+tag, +dc) and render `templateText` against it.
+// Returns nullptr + *errOut on a bad body or a template error.
+char* cp_watch_render(const char* templateText, const char* healthBodyJson,
+                      const char* name, const char* tag, const char* dc,
+                      char** errOut) {
+  try {
+    bool ok = true;
+    auto entries = parseHealthEntries(healthBodyJson, &ok);
+    if (!ok) {
+      if (errOut) *errOut = dupString("could not parse health response body");
+      return nullptr;
+    }
+    Template tmpl = Template::parse(templateText);
+    return dupString(tmpl.render(
+        buildRenderData(name, tag ? tag : "", dc ? dc : "", entries)));
   } catch (const std::exception& e) {
     if (errOut) *errOut = dupString(e.what());
     return nullptr;

@@ -18,15 +18,17 @@ namespace {
 
 struct Value;
 using ValueList = std::vector<Value>;
+using ValueMap = std::map<std::string, Value>;
 
 struct Value {
-  enum class Kind { Nil, Str, Int, Float, Bool, List };
+  enum class Kind { Nil, Str, Int, Float, Bool, List, Map };
   Kind kind = Kind::Nil;
   std::string s;
   int64_t i = 0;
   double f = 0;
   bool b = false;
   std::shared_ptr<ValueList> list;
+  std::shared_ptr<ValueMap> map;
 
   static Value nil() { return Value{}; }
   static Value str(std::string v) {
@@ -59,6 +61,19 @@ struct Value {
     r.list = std::make_shared<ValueList>(std::move(v));
     return r;
   }
+  static Value mkmap(ValueMap v) {
+    Value r;
+    r.kind = Kind::Map;
+    r.map = std::make_shared<ValueMap>(std::move(v));
+    return r;
+  }
+
+  // .key on a map; a missing key is the zero value "" (missingkey=zero)
+  Value field(const std::string& key) const {
+    if (kind != Kind::Map) return Value::str("");
+    auto it = map->find(key);
+    return it == map->end() ? Value::str("") : it->second;
+  }
 
   bool truthy() const {
     switch (kind) {
@@ -68,6 +83,7 @@ struct Value {
       case Kind::Float: return f != 0;
       case Kind::Bool: return b;
       case Kind::List: return list && !list->empty();
+      case Kind::Map: return map && !map->empty();
     }
     return false;
   }
@@ -90,6 +106,17 @@ struct Value {
           if (!first) out += " ";
           first = false;
           out += e.print();
+        }
+        return out + "]";
+      }
+      case Kind::Map: {
+        // fmt's map[k:v k:v], keys sorted
+        std::string out = "map[";
+        bool first = true;
+        for (auto& kv : *map) {
+          if (!first) out += " ";
+          first = false;
+          out += kv.first + ":" + kv.second.print();
         }
         return out + "]";
       }
@@ -121,7 +148,7 @@ using ExprPtr = std::shared_ptr<Expr>;
 
 struct Expr {
   enum class Kind { Field, Var, StrLit, NumLit, Call, Pipeline, Dot } kind;
-  std::vector<std::string> path;  // Field: .A.B  / Var: name
+  std::vector<std::string> path;  // Field: .A.B  / Var: name, then .A.B
   std::string strval;
   Value numval;
   std::string fname;            // Call
@@ -155,7 +182,10 @@ struct ActionTok {
 
 class ActionLexer {
  public:
-  explicit ActionLexer(std::string s) : s_(std::move(s)) {}
+  // varFields: lex $v.A.B as one variable token with a field path (data
+  // templates). Config templates keep their lexing: '$v' ends at the '.'.
+  ActionLexer(std::string s, bool varFields)
+      : s_(std::move(s)), varFields_(varFields) {}
 
   ActionTok next() {
     skipWs();
@@ -190,6 +220,14 @@ class ActionLexer {
       while (pos_ < s_.size() &&
              (isalnum((unsigned char)s_[pos_]) || s_[pos_] == '_'))
         name += s_[pos_++];
+      // $v.A.B: the field path rides along after the first '.'
+      while (varFields_ && pos_ + 1 < s_.size() && s_[pos_] == '.' &&
+             (isalpha((unsigned char)s_[pos_ + 1]) || s_[pos_ + 1] == '_')) {
+        name += s_[pos_++];
+        while (pos_ < s_.size() &&
+               (isalnum((unsigned char)s_[pos_]) || s_[pos_] == '_'))
+          name += s_[pos_++];
+      }
       return {ActionTok::Kind::Var, name, {}};
     }
     if (isdigit((unsigned char)c) || c == '-' || c == '+') {
@@ -222,6 +260,7 @@ class ActionLexer {
 
  private:
   std::string s_;
+  bool varFields_;
   size_t pos_ = 0;
 
   void skipWs() {
@@ -270,7 +309,10 @@ std::vector<std::string> splitPath(const std::string& p) {
 
 class ActionParser {
  public:
-  explicit ActionParser(std::string s) : lex_(std::move(s)) { advance(); }
+  ActionParser(std::string s, bool varFields)
+      : lex_(std::move(s), varFields) {
+    advance();
+  }
 
   // parse full pipeline (for action body)
   ExprPtr parsePipeline() {
@@ -359,11 +401,16 @@ class ActionParser {
         }
         advance();
         return e;
-      case ActionTok::Kind::Var:
+      case ActionTok::Kind::Var: {
         e->kind = Expr::Kind::Var;
-        e->path = {tok_.text};
+        size_t dot = tok_.text.find('.');
+        e->path = {tok_.text.substr(0, dot)};
+        if (dot != std::string::npos)
+          for (auto& f : splitPath(tok_.text.substr(dot)))
+            e->path.push_back(f);
         advance();
         return e;
+      }
       case ActionTok::Kind::Str:
         e->kind = Expr::Kind::StrLit;
         e->strval = tok_.text;
@@ -397,7 +444,8 @@ struct RawAction {
 
 class TemplateParser {
  public:
-  explicit TemplateParser(const std::string& text) : text_(text) {}
+  TemplateParser(const std::string& text, bool dataMode)
+      : text_(text), dataMode_(dataMode) {}
 
   std::vector<NodePtr> parse() {
     auto nodes = parseNodes(nullptr);
@@ -406,6 +454,7 @@ class TemplateParser {
 
  private:
   const std::string& text_;
+  bool dataMode_;
   size_t pos_ = 0;
   bool pendingTrim_ = false;  // previous action had a right-trim marker
   int depth_ = 0;
@@ -468,7 +517,7 @@ class TemplateParser {
       if (keyword == "range") {
         auto node = std::make_shared<Node>();
         node->kind = Node::Kind::Range;
-        ActionParser ap(trimmed.substr(5));
+        ActionParser ap(trimmed.substr(5), dataMode_);
         auto vars = ap.parseRangeVars();
         node->rangeVar = vars.first;
         node->rangeVar2 = vars.second;
@@ -482,7 +531,7 @@ class TemplateParser {
       }
       // assignment action: {{ $x := expr }}
       {
-        ActionParser ap(trimmed);
+        ActionParser ap(trimmed, dataMode_);
         auto assign = ap.tryParseAssignment();
         if (!assign.first.empty()) {
           auto node = std::make_shared<Node>();
@@ -496,7 +545,7 @@ class TemplateParser {
       // plain action
       auto node = std::make_shared<Node>();
       node->kind = Node::Kind::Action;
-      ActionParser ap(trimmed);
+      ActionParser ap(trimmed, dataMode_);
       node->expr = ap.parsePipeline();
       nodes.push_back(node);
     }
@@ -511,7 +560,7 @@ class TemplateParser {
     bool isWith = firstWord(header) == "with";
     auto node = std::make_shared<Node>();
     node->kind = isWith ? Node::Kind::With : Node::Kind::If;
-    ActionParser ap(header.substr(isWith ? 4 : 2));
+    ActionParser ap(header.substr(isWith ? 4 : 2), dataMode_);
     node->expr = ap.parsePipeline();
     std::string term;
     node->body = parseNodes(&term);
@@ -716,12 +765,18 @@ Value fnLen(const std::vector<Value>& args) {
   const Value& v = args[0];
   if (v.kind == Value::Kind::List) return Value::integer((int64_t)v.list->size());
   if (v.kind == Value::Kind::Str) return Value::integer((int64_t)v.s.size());
+  if (v.kind == Value::Kind::Map) return Value::integer((int64_t)v.map->size());
   throw std::runtime_error("template: len of unsupported type");
 }
 
 Value fnIndex(const std::vector<Value>& args) {
   if (args.size() != 2)
     throw std::runtime_error("template: wrong number of args for index");
+  if (args[0].kind == Value::Kind::Map) {
+    if (args[1].kind != Value::Kind::Str)
+      throw std::runtime_error("template: index of map needs a string key");
+    return args[0].field(args[1].s);
+  }
   int64_t i = args[1].toInt();
   if (args[0].kind == Value::Kind::List) {
     if (i < 0 || (size_t)i >= args[0].list->size())
@@ -821,6 +876,17 @@ class Evaluator {
     return out;
   }
 
+  // data mode: "." (and "$") start as `data` instead of the environment
+  std::string exec(const std::vector<NodePtr>& nodes, const Value& data) {
+    Scope scope;
+    scope.dot = data;
+    scope.dotIsEnv = false;
+    scope.vars[""] = data;
+    std::string out;
+    execNodes(nodes, scope, out);
+    return out;
+  }
+
  private:
   std::map<std::string, std::string> env_;
 
@@ -892,8 +958,10 @@ class Evaluator {
         return scope.dot;
       case Expr::Kind::Field: {
         if (!scope.dotIsEnv) {
-          // field access on a non-map value: missingkey=zero -> empty
-          return Value::str("");
+          // missing key, or a field of a non-map value: missingkey=zero
+          Value v = scope.dot;
+          for (auto& key : e->path) v = v.field(key);
+          return v;
         }
         // .A -> env lookup; missing key = zero value ("")
         auto it = env_.find(e->path[0]);
@@ -906,7 +974,9 @@ class Evaluator {
         if (it == scope.vars.end())
           throw std::runtime_error("template: undefined variable $" +
                                    e->path[0]);
-        return it->second;
+        Value v = it->second;
+        for (size_t i = 1; i < e->path.size(); i++) v = v.field(e->path[i]);
+        return v;
       }
       case Expr::Kind::Call: {
         std::vector<Value> args;
@@ -990,10 +1060,50 @@ class Evaluator {
   }
 };
 
+Value fromJson(const Json& j) {
+  switch (j.type()) {
+    case Json::Type::Null: return Value::nil();
+    case Json::Type::Bool: return Value::boolean(j.boolean());
+    case Json::Type::Int: return Value::integer(j.asInt());
+    case Json::Type::Double: return Value::number(j.asDouble());
+    case Json::Type::String: return Value::str(j.str());
+    case Json::Type::Array: {
+      ValueList out;
+      for (auto& e : j.array()) out.push_back(fromJson(e));
+      return Value::mklist(std::move(out));
+    }
+    case Json::Type::Object: {
+      ValueMap out;
+      for (auto& kv : j.object()) out[kv.first] = fromJson(kv.second);
+      return Value::mkmap(std::move(out));
+    }
+  }
+  return Value::nil();
+}
+
 }  // namespace
 
+struct Template::Impl {
+  std::vector<NodePtr> nodes;
+};
+
+Template Template::parse(const std::string& text) {
+  auto impl = std::make_shared<Impl>();
+  TemplateParser parser(text, true);
+  impl->nodes = parser.parse();
+  Template t;
+  t.impl_ = std::move(impl);
+  return t;
+}
+
+std::string Template::render(const Json& data) const {
+  if (!impl_) throw std::runtime_error("template: not parsed");
+  Evaluator ev;
+  return ev.exec(impl_->nodes, fromJson(data));
+}
+
 std::string renderTemplate(const std::string& text) {
-  TemplateParser parser(text);
+  TemplateParser parser(text, false);
   auto nodes = parser.parse();
   Evaluator ev;
   return ev.exec(nodes);

@@ -1,10 +1,88 @@
 #include "cpilot/watches.hpp"
 
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+#include <cerrno>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <sstream>
+#include <tuple>
+
 #include "cpilot/decode.hpp"
 #include "cpilot/ips.hpp"
 #include "cpilot/log.hpp"
 
 namespace cpilot {
+
+namespace {
+
+bool readWholeFile(const std::string& path, std::string* out) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) return false;
+  std::stringstream ss;
+  ss << f.rdbuf();
+  if (f.bad()) return false;
+  *out = ss.str();
+  return true;
+}
+
+// watches[].render: shape only
+bool newRenderConfig(const Json& raw, const std::string& watchName,
+                     std::shared_ptr<RenderConfig>* out, std::string* err) {
+  const std::string where = "watch[" + watchName + "].render";
+  if (!raw.isObject()) {
+    *err = where + " must be an object";
+    return false;
+  }
+  if (!decode::checkKeys(raw, {"source", "dest", "mode"}, err)) {
+    *err = where + ": " + *err;
+    return false;
+  }
+  auto cfg = std::make_shared<RenderConfig>();
+  struct {
+    const char* key;
+    std::string* field;
+  } paths[] = {{"source", &cfg->source}, {"dest", &cfg->dest}};
+  for (auto& p : paths) {
+    const Json* v = raw.find(p.key);
+    if (!v) {
+      *err = where + "." + p.key + " is required";
+      return false;
+    }
+    if (!v->isString() || v->str().empty()) {
+      *err = where + "." + p.key + " must be a non-empty string";
+      return false;
+    }
+    if (v->str()[0] != '/') {
+      *err = where + "." + p.key + " must be an absolute path";
+      return false;
+    }
+    *p.field = v->str();
+  }
+  if (cfg->source == cfg->dest) {
+    *err = where + ".dest must differ from source";
+    return false;
+  }
+  if (const Json* v = raw.find("mode")) {
+    const std::string& m = v->str();
+    bool octal = v->isString() && (m.size() == 3 || m.size() == 4) &&
+                 m.find_first_not_of("01234567") == std::string::npos;
+    long mode = octal ? strtol(m.c_str(), nullptr, 8) : -1;
+    if (mode < 0 || mode > 0777) {
+      *err = where + ".mode must be an octal string from \"0000\" to \"0777\"";
+      return false;
+    }
+    cfg->mode = (mode_t)mode;
+  }
+  *out = std::move(cfg);
+  return true;
+}
+
+}  // namespace
 
 bool newWatchConfigs(const Json& rawWatches,
                      std::vector<std::shared_ptr<WatchConfig>>* out,
@@ -20,8 +98,9 @@ bool newWatchConfigs(const Json& rawWatches,
       *err = "Watch configuration error: watch must be an object";
       return false;
     }
-    if (!decode::checkKeys(raw, {"name", "interval", "tag", "dc", "blocking"},
-                           err)) {
+    if (!decode::checkKeys(
+            raw, {"name", "interval", "tag", "dc", "blocking", "render"},
+            err)) {
       *err = "Watch configuration error: " + *err;
       return false;
     }
@@ -44,8 +123,104 @@ bool newWatchConfigs(const Json& rawWatches,
       *err = "watch[" + cfg->serviceName + "].interval must be > 0";
       return false;
     }
+    if (const Json* v = raw.find("render")) {
+      if (!v->isNull() &&
+          !newRenderConfig(*v, cfg->serviceName, &cfg->render, err))
+        return false;
+    }
     out->push_back(cfg);
   }
+  return true;
+}
+
+bool loadRenderTemplate(WatchConfig& cfg, std::string* err) {
+  if (!cfg.render) return true;
+  const std::string where = "watch[" + cfg.serviceName + "].render.source: ";
+  std::string text;
+  errno = 0;
+  if (!readWholeFile(cfg.render->source, &text)) {
+    *err = where + "open " + cfg.render->source + ": " +
+           strerror(errno ? errno : EIO);
+    return false;
+  }
+  try {
+    cfg.render->tmpl = Template::parse(text);
+  } catch (const std::exception& e) {
+    *err = where + e.what();
+    return false;
+  }
+  return true;
+}
+
+Json buildRenderData(const std::string& serviceName, const std::string& tag,
+                     const std::string& dc,
+                     const std::vector<ServiceEntry>& entries) {
+  struct Row {
+    std::string address;
+    const ServiceEntry* e;
+  };
+  std::vector<Row> rows;
+  for (auto& e : entries)
+    rows.push_back({e.address.empty() ? e.nodeAddress : e.address, &e});
+  std::sort(rows.begin(), rows.end(), [](const Row& a, const Row& b) {
+    return std::tie(a.address, a.e->port, a.e->id) <
+           std::tie(b.address, b.e->port, b.e->id);
+  });
+  JsonArray services;
+  for (auto& r : rows) {
+    JsonArray tags;
+    for (auto& t : r.e->tags) tags.push_back(Json(t));
+    services.push_back(Json(JsonObject{
+        {"ID", Json(r.e->id)},
+        {"Name", Json(serviceName)},
+        {"Address", Json(r.address)},
+        {"Port", Json(r.e->port)},
+        {"Tags", Json(std::move(tags))},
+        {"Node", Json(r.e->node)},
+        {"NodeAddress", Json(r.e->nodeAddress)},
+    }));
+  }
+  return Json(JsonObject{
+      {"Name", Json(serviceName)},
+      {"Tag", Json(tag)},
+      {"DC", Json(dc)},
+      {"Healthy", Json(!entries.empty())},
+      {"Services", Json(std::move(services))},
+  });
+}
+
+bool writeFileAtomic(const std::string& dest, const std::string& bytes,
+                     mode_t mode, std::string* err) {
+  std::string current;
+  if (readWholeFile(dest, &current) && current == bytes) return true;
+
+  std::string tmp = dest + ".tmp.XXXXXX";
+  int fd = mkostemp(&tmp[0], O_CLOEXEC);
+  if (fd < 0) {
+    *err = "create " + tmp + ": " + strerror(errno);
+    return false;
+  }
+  auto fail = [&](const char* what) {
+    *err = std::string(what) + " " + tmp + ": " + strerror(errno);
+    if (fd >= 0) close(fd);
+    unlink(tmp.c_str());
+    return false;
+  };
+  // mkostemp creates 0600; fchmod sets the mode whatever the umask is
+  if (fchmod(fd, mode) != 0) return fail("chmod");
+  size_t off = 0;
+  while (off < bytes.size()) {
+    ssize_t n = write(fd, bytes.data() + off, bytes.size() - off);
+    if (n < 0) {
+      if (errno == EINTR) continue;
+      return fail("write");
+    }
+    off += (size_t)n;
+  }
+  int rc = close(fd);
+  fd = -1;
+  if (rc != 0) return fail("close");
+  if (rename(tmp.c_str(), dest.c_str()) != 0) return fail("rename");
   return true;
 }
 
@@ -78,6 +253,17 @@ void Watch::onResult(bool ok, std::vector<ServiceEntry> entries) {
   consul_->watchGauge()->set({serviceName_}, (double)entries.size());
   bool isHealthy = !entries.empty();
   bool didChange = consul_->compareAndSwap(serviceName_, entries);
+  // the file is in place before anything hears about this result; the
+  // first result of a generation renders even when nothing changed, so
+  // dest exists before anything depends on it
+  if (render_ && (didChange || !rendered_)) {
+    rendered_ = true;
+    std::string err;
+    if (!renderDest(entries, &err)) {
+      LOG_ERROR("%s: render: %s", name_.c_str(), err.c_str());
+      bus_->publish(Event{EventCode::Error, name_ + ": render: " + err});
+    }
+  }
   if (didChange) {
     bus_->publish(Event{EventCode::StatusChanged, name_});
     if (isHealthy)
@@ -85,6 +271,19 @@ void Watch::onResult(bool ok, std::vector<ServiceEntry> entries) {
     else
       bus_->publish(Event{EventCode::StatusUnhealthy, name_});
   }
+}
+
+bool Watch::renderDest(const std::vector<ServiceEntry>& entries,
+                       std::string* err) {
+  std::string out;
+  try {
+    out = render_->tmpl.render(
+        buildRenderData(serviceName_, tag_, dc_, entries));
+  } catch (const std::exception& e) {
+    *err = e.what();
+    return false;
+  }
+  return writeFileAtomic(render_->dest, out, render_->mode, err);
 }
 
 void Watch::tick() {
