@@ -27,6 +27,13 @@ def _load():
             ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
         _lib.cp_parse_duration_ns.restype = ctypes.c_longlong
         _lib.cp_parse_duration_ns.argtypes = [ctypes.c_char_p]
+        _lib.cp_parse_duration.restype = ctypes.c_int
+        _lib.cp_parse_duration.argtypes = [
+            ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong)]
+        _lib.cp_render_data.restype = ctypes.c_void_p
+        _lib.cp_render_data.argtypes = [
+            ctypes.c_char_p, ctypes.c_char_p,
+            ctypes.POINTER(ctypes.c_void_p)]
         _lib.cp_json5_to_json.restype = ctypes.c_void_p
         _lib.cp_json5_to_json.argtypes = [
             ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
@@ -70,6 +77,28 @@ def parse_duration_ns(text):
     if ns < 0:
         raise ValueError("invalid duration: %s" % text)
     return ns
+
+
+def parse_duration(text):
+    """Like parse_duration_ns, but negative durations are values too: returns
+    the nanoseconds (any int64) or raises ValueError."""
+    ns = ctypes.c_longlong()
+    if not _load().cp_parse_duration(text.encode(), ctypes.byref(ns)):
+        raise ValueError("invalid duration: %s" % text)
+    return ns.value
+
+
+def render_data(template_text, data_json):
+    """Render a data template (the language of a watch's `render` file)
+    against the JSON document `data_json`. Raises ValueError on a bad
+    document or a template error."""
+    lib = _load()
+    err = ctypes.c_void_p()
+    out = lib.cp_render_data(template_text.encode(), data_json.encode(),
+                             ctypes.byref(err))
+    if not out:
+        raise ValueError(_take_string(lib, err.value))
+    return _take_string(lib, out)
 
 
 def json5_to_json(text):

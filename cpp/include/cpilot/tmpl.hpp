@@ -4,10 +4,13 @@
 // watch render files) against a JSON value.
 //
 // Supported: {{ .VAR }} lookups, {{- -}} whitespace trimming, variables
-// ($i), pipelines (a | b | c), nested calls with parens, string/number
-// literals, if/else/end, range/end (incl. `range $i := ...`), and the
-// functions: default, env, split, join, replaceAll, regexReplaceAll, loop,
-// printf.
+// with Go 1.9 block scoping ($x := ..., also in if/with/range headers),
+// pipelines (a | b | c), nested calls with parens, Go string, number and
+// bool constants, if/else if/else, with/else, range/else (one and two
+// variables), comments, the Go builtins, and the functions: default, env,
+// split, join, replaceAll, regexReplaceAll, loop. Whatever Go would
+// refuse, or the engine cannot honour exactly, is an error; the deliberate
+// exceptions are listed in COMPONENTS.md.
 // Parity: /root/reference/config/template/template.go:19-180.
 #pragma once
 

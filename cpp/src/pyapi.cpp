@@ -41,6 +41,20 @@ char* cp_render_template(const char* text, char** errOut) {
   }
 }
 
+// Render a data template (the language of a watch's `render` file) against
+// an arbitrary JSON value: "." and "$" start as that value.
+// Returns nullptr + *errOut on a bad document or a template error.
+char* cp_render_data(const char* templateText, const char* dataJson,
+                     char** errOut) {
+  try {
+    Json data = parseJson5(dataJson);
+    return dupString(Template::parse(templateText).render(data));
+  } catch (const std::exception& e) {
+    if (errOut) *errOut = dupString(e.what());
+    return nullptr;
+  }
+}
+
 // Parse a duration (JSON5 value text: bare int or quoted string).
 // Returns nanoseconds, or -1 on error.
 long long cp_parse_duration_ns(const char* text) {
@@ -49,6 +63,19 @@ long long cp_parse_duration_ns(const char* text) {
     return (long long)parseDuration(v).count();
   } catch (const std::exception&) {
     return -1;
+  }
+}
+
+// Same input as cp_parse_duration_ns, but a negative duration and an error
+// stay apart: returns 1 and fills *outNs, or returns 0 on error.
+int cp_parse_duration(const char* text, long long* outNs) {
+  try {
+    Json v = parseJson5(text);
+    long long ns = (long long)parseDuration(v).count();
+    if (outNs) *outNs = ns;
+    return 1;
+  } catch (const std::exception&) {
+    return 0;
   }
 }
 

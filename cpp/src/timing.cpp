@@ -1,52 +1,128 @@
 #include "cpilot/timing.hpp"
 
 #include <cctype>
-#include <cmath>
+#include <cstdint>
 #include <cstdlib>
 
 namespace cpilot {
 
-Duration parseGoDuration(const std::string& s) {
-  // Go time.ParseDuration grammar: [-+]?([0-9]*(\.[0-9]*)?[a-z]+)+
-  // "0" is allowed without a unit.
-  if (s.empty()) throw std::runtime_error("time: invalid duration " + s);
+namespace {
+
+constexpr uint64_t kTwo63 = (uint64_t)1 << 63;
+
+[[noreturn]] void invalidDuration(const std::string& s) {
+  throw std::runtime_error("time: invalid duration " + s);
+}
+
+// [+-]?[0-9]+ that fits an int64: what strconv.Atoi accepts
+bool strictAtoi(const std::string& s, int64_t* out) {
   size_t i = 0;
   bool neg = false;
-  if (s[i] == '+' || s[i] == '-') {
-    neg = (s[i] == '-');
-    i++;
+  if (i < s.size() && (s[i] == '+' || s[i] == '-')) neg = s[i++] == '-';
+  if (i == s.size()) return false;
+  uint64_t v = 0;
+  for (; i < s.size(); i++) {
+    if (s[i] < '0' || s[i] > '9') return false;
+    uint64_t d = (uint64_t)(s[i] - '0');
+    if (v > (kTwo63 - d) / 10) return false;
+    v = v * 10 + d;
   }
+  if (!neg && v == kTwo63) return false;
+  *out = neg ? (int64_t)(0 - v) : (int64_t)v;
+  return true;
+}
+
+Duration secondsToDuration(int64_t sec) {
+  constexpr int64_t kMaxSec = INT64_MAX / 1000000000;
+  if (sec > kMaxSec || sec < -kMaxSec)
+    throw std::runtime_error("time: duration of " + std::to_string(sec) +
+                             " seconds overflows");
+  return Duration(sec * 1000000000);
+}
+
+}  // namespace
+
+Duration parseGoDuration(const std::string& orig) {
+  // Go time.ParseDuration: [-+]?([0-9]*(\.[0-9]*)?[a-z]+)+ accumulated in
+  // an unsigned integer; any step past 2^63 is an error, as is a positive
+  // total past 2^63-1. "0" is allowed without a unit.
+  size_t i = 0;
+  const std::string& s = orig;
+  bool neg = false;
+  if (i < s.size() && (s[i] == '+' || s[i] == '-')) neg = s[i++] == '-';
   if (s.compare(i, std::string::npos, "0") == 0) return Duration(0);
-  if (i == s.size()) throw std::runtime_error("time: invalid duration " + s);
-  double totalNs = 0;
+  if (i == s.size()) invalidDuration(orig);
+  uint64_t total = 0;
   while (i < s.size()) {
+    if (!(s[i] == '.' || (s[i] >= '0' && s[i] <= '9'))) invalidDuration(orig);
+    // [0-9]*
+    uint64_t v = 0;
     size_t start = i;
-    while (i < s.size() && (isdigit((unsigned char)s[i]) || s[i] == '.')) i++;
+    for (; i < s.size() && s[i] >= '0' && s[i] <= '9'; i++) {
+      if (v > kTwo63 / 10) invalidDuration(orig);
+      v = v * 10 + (uint64_t)(s[i] - '0');
+      if (v > kTwo63) invalidDuration(orig);
+    }
+    bool pre = i != start;
+    // (\.[0-9]*)? -- digits past what fits are dropped, as Go does
+    uint64_t frac = 0;
+    double scale = 1;
+    bool post = false;
+    if (i < s.size() && s[i] == '.') {
+      i++;
+      start = i;
+      bool overflow = false;
+      for (; i < s.size() && s[i] >= '0' && s[i] <= '9'; i++) {
+        if (overflow) continue;
+        if (frac > (kTwo63 - 1) / 10) {
+          overflow = true;
+          continue;
+        }
+        uint64_t y = frac * 10 + (uint64_t)(s[i] - '0');
+        if (y > kTwo63) {
+          overflow = true;
+          continue;
+        }
+        frac = y;
+        scale *= 10;
+      }
+      post = i != start;
+    }
+    if (!pre && !post) invalidDuration(orig);
+    // unit: everything up to the next digit or dot
+    start = i;
+    while (i < s.size() && s[i] != '.' && !(s[i] >= '0' && s[i] <= '9')) i++;
     if (i == start)
-      throw std::runtime_error("time: invalid duration " + s);
-    double v = strtod(s.substr(start, i - start).c_str(), nullptr);
-    // unit
-    size_t ustart = i;
-    while (i < s.size() && !isdigit((unsigned char)s[i]) && s[i] != '.') i++;
-    std::string unit = s.substr(ustart, i - ustart);
-    double mult;
+      throw std::runtime_error("time: missing unit in duration " + orig);
+    std::string unit = s.substr(start, i - start);
+    uint64_t mult;
     if (unit == "ns") mult = 1;
-    else if (unit == "us" || unit == "µs" || unit == "μs") mult = 1e3;
-    else if (unit == "ms") mult = 1e6;
-    else if (unit == "s") mult = 1e9;
-    else if (unit == "m") mult = 60e9;
-    else if (unit == "h") mult = 3600e9;
+    else if (unit == "us" || unit == "\xc2\xb5s" || unit == "\xce\xbcs")
+      mult = 1000;
+    else if (unit == "ms") mult = 1000000;
+    else if (unit == "s") mult = 1000000000;
+    else if (unit == "m") mult = 60000000000ULL;
+    else if (unit == "h") mult = 3600000000000ULL;
     else
       throw std::runtime_error("time: unknown unit \"" + unit +
-                               "\" in duration " + s);
-    totalNs += v * mult;
+                               "\" in duration " + orig);
+    if (v > kTwo63 / mult) invalidDuration(orig);
+    v *= mult;
+    if (frac > 0) {
+      // the one float step Go takes: frac*(unit/scale) <= 3.6e12
+      v += (uint64_t)((double)frac * ((double)mult / scale));
+      if (v > kTwo63) invalidDuration(orig);
+    }
+    total += v;
+    if (total > kTwo63) invalidDuration(orig);
   }
-  if (neg) totalNs = -totalNs;
-  return Duration((int64_t)totalNs);
+  if (neg) return Duration((int64_t)(0 - total));
+  if (total > kTwo63 - 1) invalidDuration(orig);
+  return Duration((int64_t)total);
 }
 
 Duration parseDuration(const Json& v) {
-  if (v.isInt()) return std::chrono::seconds(v.asInt());
+  if (v.isInt()) return secondsToDuration(v.asInt());
   if (v.isDouble()) {
     // the reference only accepts integer types here; a JSON5 float is an
     // error ("unexpected duration of type float64")
@@ -54,11 +130,10 @@ Duration parseDuration(const Json& v) {
   }
   if (v.isString()) {
     const std::string& s = v.str();
-    // integer-only string = seconds (duration.go:53-55)
-    char* end = nullptr;
-    long val = strtol(s.c_str(), &end, 10);
-    if (!s.empty() && end && *end == '\0')
-      return std::chrono::seconds(val);
+    // a string strconv.Atoi accepts = seconds, parsed as "<n>s"
+    // (duration.go:53-55), so it overflows like any other duration
+    int64_t sec = 0;
+    if (strictAtoi(s, &sec)) return parseGoDuration(std::to_string(sec) + "s");
     return parseGoDuration(s);
   }
   throw std::runtime_error("unexpected duration type");

@@ -135,9 +135,11 @@ void testEngineOnData() {
   // and renderTemplate still renders against the environment
   CHECK_EQ(renderTemplate("{{ .CPILOT_RENDERTEST_VAR }}"),
            std::string("from-env"));
-  // ... with its lexing untouched: there `$v` still ends at the '.', and
-  // the stray field after it is ignored as it always was
+  // ... with the same lexing: `$v.Field` is a field of `$v` there too (a
+  // field of a string renders empty), not `$v` with a stray token dropped
   CHECK_EQ(renderTemplate("{{ $v := .CPILOT_RENDERTEST_VAR }}{{ $v.Field }}"),
+           std::string(""));
+  CHECK_EQ(renderTemplate("{{ $v := .CPILOT_RENDERTEST_VAR }}{{ $v }}"),
            std::string("from-env"));
 
   // range over a map field that is not a list: the existing error

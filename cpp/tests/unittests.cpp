@@ -140,6 +140,46 @@ static void testDurations() {
     threw = true;
   }
   CHECK(threw);
+
+  // Go's ParseDuration accumulates integers: no float rounding, the digit
+  // rules, overflow is an error and both int64 bounds are reachable
+  auto ns = [](const char* s) { return parseDuration(Json(s)).count(); };
+  auto bad = [](const char* s) {
+    try {
+      parseDuration(Json(s));
+    } catch (const std::exception&) {
+      return true;
+    }
+    return false;
+  };
+  CHECK_EQ(ns("1.001s"), (int64_t)1001000000);
+  CHECK_EQ(ns("-5"), (int64_t)-5000000000LL);
+  CHECK_EQ(ns(".5s"), (int64_t)500000000);
+  CHECK_EQ(ns("1.s"), (int64_t)1000000000);
+  CHECK_EQ(ns("100\xc2\xb5s"), (int64_t)100000);
+  CHECK_EQ(ns("2562047h47m16.854775807s"), INT64_MAX);
+  CHECK_EQ(ns("-2562047h47m16.854775808s"), INT64_MIN);
+  CHECK_EQ(ns("9223372036854775807ns"), INT64_MAX);
+  CHECK(bad("1.2.3s"));
+  CHECK(bad(".s"));
+  CHECK(bad(" 5"));
+  CHECK(bad("5 "));
+  CHECK(bad("1S"));
+  CHECK(bad("1d"));
+  CHECK(bad("1.5"));
+  CHECK(bad("9223372037s"));
+  CHECK(bad("9223372037"));
+  CHECK(bad("100000000000000000000ns"));
+  CHECK(bad("9223372036854775808ns"));
+  CHECK(bad("2562047h47m16.854775808s"));
+  CHECK(bad("-9223372036854775809ns"));
+  threw = false;
+  try {
+    parseDuration(Json((int64_t)9223372037LL));
+  } catch (...) {
+    threw = true;
+  }
+  CHECK(threw);
 }
 
 static void testTemplate() {
@@ -234,6 +274,84 @@ static void testTemplate() {
                "{{ range $i, $v := loop 5 8 }}{{ $i }}:{{ $v }} {{ end }}"),
            std::string("0:5 1:6 2:7 "));
   unsetenv("STAGE");
+
+  // Go 1.9 semantics the engine has to match (the same rows, and many
+  // more, are in tests/golden/template_cases.json)
+  auto fails = [](const char* t) {
+    try {
+      renderTemplate(t);
+    } catch (const std::exception&) {
+      return true;
+    }
+    return false;
+  };
+  setenv("FOO", "abc", 1);
+  unsetenv("MISSING");
+  CHECK_EQ(renderTemplate(
+               "{{ range split \",\" .MISSING }}x{{ else }}none{{ end }}"),
+           std::string("none"));
+  CHECK_EQ(renderTemplate("{{ $x := \"a\" }}{{ if \"y\" }}{{ $x := \"b\" }}"
+                          "{{ end }}{{ $x }}"),
+           std::string("a"));
+  CHECK(fails("{{ if \"y\" }}{{ $z := 1 }}{{ end }}{{ $z }}"));
+  CHECK_EQ(renderTemplate("{{ if true }}y{{ end }}{{ false }}"),
+           std::string("yfalse"));
+  CHECK(fails("{{ .FOO bar }}"));
+  CHECK(fails("{{ .FOO \"x\" }}"));
+  CHECK(fails("{{ (.FOO).X }}"));
+  CHECK(fails("{{ end x }}"));
+  CHECK_EQ(renderTemplate("{{ 0x10 }} {{ 010 }} {{ 1e3 }}"),
+           std::string("16 8 1000"));
+  CHECK_EQ(renderTemplate("{{ with $x := .FOO }}{{ $x }}{{ end }}"
+                          "{{ if $y := .FOO }}{{ $y }}{{ end }}"),
+           std::string("abcabc"));
+  CHECK_EQ(renderTemplate("{{ \"a}}b\" }}{{/* }} */}}"), std::string("a}}b"));
+  CHECK_EQ(renderTemplate("{{ \"\\x41\\u00e9\\\\\" }}"),
+           std::string("A\xc3\xa9\\"));
+  CHECK(fails("{{ \"\\q\" }}"));
+  CHECK_EQ(renderTemplate("{{ regexReplaceAll \"(a)\" \"${1}x\" \"a\" }}"),
+           std::string("ax"));
+  CHECK_EQ(renderTemplate("{{ regexReplaceAll \"(a)\" \"$1x\" \"a\" }}"),
+           std::string(""));
+  CHECK_EQ(renderTemplate("{{ regexReplaceAll \"a\" \"[$&]\" \"a\" }}"),
+           std::string("[$&]"));
+  CHECK_EQ(renderTemplate("{{ regexReplaceAll \"x*\" \"-\" \"abxd\" }}"),
+           std::string("-a-b-d-"));
+  CHECK_EQ(renderTemplate("{{ regexReplaceAll \".\" \"x\" \"\xc3\xa9\" }}"),
+           std::string("x"));
+  CHECK_EQ(renderTemplate("{{ regexReplaceAll \"(?i)A\" \"b\" \"aA\" }}"),
+           std::string("bb"));
+  CHECK_EQ(renderTemplate(
+               "{{ regexReplaceAll \"(?P<n>a)\" \"${n}$n\" \"a\" }}"),
+           std::string("aa"));
+  CHECK(fails("{{ regexReplaceAll `\\pL` \"x\" \"a\" }}"));
+  CHECK(fails("{{ regexReplaceAll `a\\z` \"x\" \"a\" }}"));
+  CHECK(fails("{{ regexReplaceAll `a(?i)b` \"x\" \"ab\" }}"));
+  CHECK(fails("{{ regexReplaceAll `(a)\\1` \"x\" \"aa\" }}"));
+  CHECK(fails("{{ regexReplaceAll `a(?=b)` \"x\" \"ab\" }}"));
+  CHECK(fails("{{ regexReplaceAll \"a\" \"x\" \"\\xff\" }}"));
+  CHECK_EQ(renderTemplate("{{ \"a\" | replaceAll \"\" \"-\" }}"),
+           std::string("-a-"));
+  CHECK_EQ(renderTemplate("{{ split \"\" \"a\xc3\xa9\" | join \",\" }}"),
+           std::string("a,\xc3\xa9"));
+  CHECK_EQ(renderTemplate("{{ 3.14159265 }} {{ .MISSING | default "
+                          "10.123456789 }} {{ 100000000000000000000.0 }} "
+                          "{{ 1e21 }} {{ 0.00001 }} {{ -0.0 }}"),
+           std::string("3.14159265 10.123456789 100000000000000000000 "
+                       "1e+21 1e-05 -0"));
+  CHECK_EQ(renderTemplate("{{ printf \"%q|%03d|%5.2f|%-4s|%x|%t|%v|%%\" "
+                          "\"a\\\"b\" 7 3.14159 \"ab\" 255 true 1.5 }}"),
+           std::string("\"a\\\"b\"|007| 3.14|ab  |ff|true|1.5|%"));
+  CHECK(fails("{{ printf \"%e\" 1.5 }}"));
+  CHECK(fails("{{ printf \"%d\" 1 2 }}"));
+  CHECK(fails("{{ loop 1.5 }}"));
+  CHECK(fails("{{ loop \" 3\" }}"));
+  CHECK(fails("{{ if true }}x"));
+  // deliberate leniencies, pinned
+  CHECK_EQ(renderTemplate("{{ eq 1 \"1\" }}[{{ .FOO.BAR }}]"
+                          "{{ index \"abc\" 1 }}{{ printf \"%d\" \"7\" }}"),
+           std::string("true[]987"));
+  unsetenv("FOO");
 }
 
 static void testEvents() {
