@@ -47,6 +47,11 @@ def _load():
             ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
             ctypes.c_char_p, ctypes.c_char_p,
             ctypes.POINTER(ctypes.c_void_p)]
+        _lib.cp_sensor_extract.restype = ctypes.c_int
+        _lib.cp_sensor_extract.argtypes = [
+            ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
+            ctypes.POINTER(ctypes.c_double),
+            ctypes.POINTER(ctypes.c_void_p)]
         _lib.cp_free.argtypes = [ctypes.c_void_p]
     return _lib
 
@@ -129,6 +134,25 @@ def consul_endpoint(consul_json):
     if not out:
         raise ValueError(_take_string(lib, err.value))
     return _take_string(lib, out)
+
+
+def sensor_extract(body, record_json):
+    """Dry-run of one `telemetry.sensors[].record` entry: the float the
+    daemon would record for the source text `body` (str or bytes), scale
+    applied. Raises ValueError with the stable reason the daemon would log
+    (bytes that are not UTF-8 are shown as U+FFFD), or with the config
+    error of a bad record."""
+    lib = _load()
+    if isinstance(body, str):
+        body = body.encode()
+    err = ctypes.c_void_p()
+    value = ctypes.c_double()
+    if not lib.cp_sensor_extract(body, len(body), record_json.encode(),
+                                 ctypes.byref(value), ctypes.byref(err)):
+        reason = ctypes.string_at(err.value).decode(errors="replace")
+        lib.cp_free(err.value)
+        raise ValueError(reason)
+    return value.value
 
 
 def watch_render(template_text, health_body_json, name, tag="", dc=""):

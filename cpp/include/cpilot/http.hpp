@@ -142,15 +142,19 @@ struct TlsOptions {
   bool insecureSkipVerify = false;
 };
 
+// ClientResult::error of a response whose body exceeds `maxBody`.
+extern const char* const kBodyTooLarge;
+
 // target: "unix:<path>" or "host:port". A unix path too long for
-// sockaddr_un is an error, never truncated.
+// sockaddr_un is an error, never truncated. maxBody > 0 caps the decoded
+// body; a larger one fails with kBodyTooLarge instead of being buffered.
 ClientResult request(const std::string& target, const std::string& method,
                      const std::string& path, const std::string& body,
                      const std::string& contentType = "application/json",
                      const std::map<std::string, std::string>& headers = {},
                      int timeoutMs = 10000,
                      const TlsOptions* tls = nullptr,
-                     CancelToken* cancel = nullptr);
+                     CancelToken* cancel = nullptr, size_t maxBody = 0);
 
 }  // namespace http
 }  // namespace cpilot

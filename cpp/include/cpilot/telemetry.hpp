@@ -14,6 +14,7 @@
 #include "cpilot/jobs.hpp"
 #include "cpilot/json.hpp"
 #include "cpilot/metrics.hpp"
+#include "cpilot/sensor.hpp"
 #include "cpilot/watches.hpp"
 
 namespace cpilot {
@@ -56,6 +57,7 @@ struct TelemetryConfig {
   std::vector<std::string> tags;
   std::string ipAddress;
   std::vector<std::shared_ptr<MetricConfig>> metricConfigs;
+  std::vector<std::shared_ptr<sensor::SensorSpec>> sensorSpecs;
   std::shared_ptr<JobConfig> jobConfig;  // synthetic "containerpilot" job
 };
 
@@ -74,7 +76,12 @@ class Telemetry {
   // Bind through http::Server::listenTcpRetrying (10x1s on a loop timer,
   // fatal after the last failed attempt); always returns true.
   bool start(std::string* err);
+  // Also stops the sensors: timers and in-flight http fetches are
+  // canceled and the sensor workers joined.
   void stop();
+
+  // Start sampling `telemetry.sensors` into `bus` (no-op without any).
+  void runSensors(const std::shared_ptr<Bus>& bus);
 
   std::vector<std::shared_ptr<Metric>>& metrics() { return metrics_; }
 
@@ -86,6 +93,7 @@ class Telemetry {
   std::shared_ptr<TelemetryConfig> cfg_;
   std::unique_ptr<http::Server> server_;
   std::vector<std::shared_ptr<Metric>> metrics_;
+  std::unique_ptr<sensor::Sensors> sensors_;
   std::vector<std::shared_ptr<Job>> jobs_;
   std::vector<std::string> watchNames_;
 };

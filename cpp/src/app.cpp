@@ -160,6 +160,7 @@ void App::startGeneration() {
     watch->run(loop_, bus_, cfg_->discovery.get());
   if (telemetry_) {
     for (auto& metric : telemetry_->metrics()) metric->run(bus_);
+    telemetry_->runSensors(bus_);
     std::string terr;
     if (!telemetry_->start(&terr))
       logging::logf(logging::Level::Fatal, "%s", terr.c_str());

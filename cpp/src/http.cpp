@@ -368,6 +368,8 @@ bool isChunked(const Headers& headers) {
 
 // ---------------- blocking client ----------------
 
+const char* const kBodyTooLarge = "response body too large";
+
 void CancelToken::arm(int fd) {
   std::lock_guard<std::mutex> l(mu_);
   fd_ = fd;
@@ -613,12 +615,13 @@ bool readMore(Transport& t, std::string* resp) {
   }
 }
 
-enum class ReadResult { Ok, Empty, Malformed, Truncated };
+enum class ReadResult { Ok, Empty, Malformed, Truncated, TooLarge };
 
 // Read incrementally: the head first, then exactly the framed body.
 // Fills status, headers and body; *bodyFramed is false when the body
 // ran to EOF, which leaves the connection unusable.
-ReadResult readResponse(Transport& t, ClientResult* result, bool* bodyFramed) {
+ReadResult readResponse(Transport& t, ClientResult* result, bool* bodyFramed,
+                        size_t maxBody) {
   std::string resp;
   size_t headerEnd;
   while ((headerEnd = resp.find("\r\n\r\n")) == std::string::npos) {
@@ -638,11 +641,14 @@ ReadResult readResponse(Transport& t, ClientResult* result, bool* bodyFramed) {
     // short success (Go's client errors the same way)
     std::string decoded;
     while (!tryDechunk(resp.substr(bodyStart), &decoded)) {
+      if (maxBody && decoded.size() > maxBody) return ReadResult::TooLarge;
       if (!readMore(t, &resp)) return ReadResult::Truncated;
     }
+    if (maxBody && decoded.size() > maxBody) return ReadResult::TooLarge;
     result->body = std::move(decoded);
   } else if (result->headers.count("content-length")) {
     size_t want = contentLength(result->headers);
+    if (maxBody && want > maxBody) return ReadResult::TooLarge;
     while (resp.size() < bodyStart + want) {
       if (!readMore(t, &resp)) return ReadResult::Truncated;
     }
@@ -650,6 +656,8 @@ ReadResult readResponse(Transport& t, ClientResult* result, bool* bodyFramed) {
   } else {
     // no framing: read to EOF, connection not reusable
     while (readMore(t, &resp)) {
+      if (maxBody && resp.size() - bodyStart > maxBody)
+        return ReadResult::TooLarge;
     }
     result->body = resp.substr(bodyStart);
     *bodyFramed = false;
@@ -672,7 +680,7 @@ ClientResult request(const std::string& target, const std::string& method,
                      const std::string& contentType,
                      const std::map<std::string, std::string>& headers,
                      int timeoutMs, const TlsOptions* tls,
-                     CancelToken* cancel) {
+                     CancelToken* cancel, size_t maxBody) {
   ClientResult result;
   if (cancel && cancel->cancelled()) {
     result.error = "cancelled";
@@ -710,7 +718,7 @@ ClientResult request(const std::string& target, const std::string& method,
       break;                   // "write failed"
     }
     bool bodyFramed = false;
-    ReadResult rr = readResponse(t, &result, &bodyFramed);
+    ReadResult rr = readResponse(t, &result, &bodyFramed, maxBody);
     if (rr == ReadResult::Empty && fromPool)
       continue;  // retry case 2: the server closed the idle connection
     if (rr == ReadResult::Empty || rr == ReadResult::Malformed) {
@@ -720,6 +728,10 @@ ClientResult request(const std::string& target, const std::string& method,
     }
     if (rr == ReadResult::Truncated) {
       result.error = "truncated response body";
+      return result;
+    }
+    if (rr == ReadResult::TooLarge) {
+      result.error = kBodyTooLarge;
       return result;
     }
     result.ok = true;

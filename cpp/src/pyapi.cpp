@@ -9,6 +9,7 @@
 #include "cpilot/config.hpp"
 #include "cpilot/discovery.hpp"
 #include "cpilot/json.hpp"
+#include "cpilot/sensor.hpp"
 #include "cpilot/timing.hpp"
 #include "cpilot/tmpl.hpp"
 #include "cpilot/version.hpp"
@@ -141,6 +142,34 @@ char* cp_watch_render(const char* templateText, const char* healthBodyJson,
   } catch (const std::exception& e) {
     if (errOut) *errOut = dupString(e.what());
     return nullptr;
+  }
+}
+
+// Dry-run of one sensor `record`: extract the number from `body` (bodyLen
+// bytes, NULs allowed) the way the daemon does and apply the scale. The
+// metric named by the record is not looked up.
+// Returns 1 and fills *out, or 0 and fills *errOut with the stable reason
+// (or the config error of a bad record).
+int cp_sensor_extract(const char* body, size_t bodyLen, const char* recordJson,
+                      double* out, char** errOut) {
+  try {
+    sensor::RecordSpec rec;
+    std::string key, err;
+    if (!sensor::parseRecord(parseJson5(recordJson), &rec, &key, &err)) {
+      if (errOut)
+        *errOut = dupString("record" + key + (key.empty() ? ": " : " ") + err);
+      return 0;
+    }
+    double value = 0;
+    if (!sensor::extract(std::string(body, bodyLen), rec, &value, &err)) {
+      if (errOut) *errOut = dupString(err);
+      return 0;
+    }
+    if (out) *out = value;
+    return 1;
+  } catch (const std::exception& e) {
+    if (errOut) *errOut = dupString(e.what());
+    return 0;
   }
 }
 

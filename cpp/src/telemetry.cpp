@@ -130,7 +130,7 @@ bool newTelemetryConfig(const Json* raw, ConsulBackend* disc,
     *err = "telemetry configuration error: must be an object";
     return false;
   }
-  if (!decode::checkKeys(*raw, {"port", "interfaces", "tags", "metrics"},
+  if (!decode::checkKeys(*raw, {"port", "interfaces", "tags", "metrics", "sensors"},
                          err)) {
     *err = "telemetry configuration error: " + *err;
     return false;
@@ -163,6 +163,12 @@ bool newTelemetryConfig(const Json* raw, ConsulBackend* disc,
 
   if (const Json* v = raw->find("metrics")) {
     if (!newMetricConfigs(*v, &cfg->metricConfigs, err)) return false;
+  }
+  if (const Json* v = raw->find("sensors")) {
+    std::map<std::string, prom::MetricType> keys;
+    for (auto& mc : cfg->metricConfigs) keys[mc->fullName] = mc->metricType;
+    if (!sensor::newSensorSpecs(*v, keys, &cfg->sensorSpecs, err))
+      return false;
   }
 
   // synthetic "containerpilot" job: TTL 15 / heartbeat 5, no check exec
@@ -202,6 +208,12 @@ Telemetry::Telemetry(Loop& loop, const std::shared_ptr<TelemetryConfig>& cfg)
     : loop_(loop), cfg_(cfg) {
   for (auto& mc : cfg->metricConfigs)
     metrics_.push_back(std::make_shared<Metric>(mc));
+  if (!cfg->sensorSpecs.empty())
+    sensors_ = std::make_unique<sensor::Sensors>(cfg->sensorSpecs);
+}
+
+void Telemetry::runSensors(const std::shared_ptr<Bus>& bus) {
+  if (sensors_) sensors_->start(loop_, bus);
 }
 
 void Telemetry::monitorJobs(const std::vector<std::shared_ptr<Job>>& jobs) {
@@ -232,6 +244,7 @@ bool Telemetry::start(std::string* err) {
 }
 
 void Telemetry::stop() {
+  if (sensors_) sensors_->stop();
   if (server_) {
     server_->stop();
     server_.reset();

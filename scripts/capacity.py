@@ -13,15 +13,25 @@ Env: CPILOT_CAPACITY_WATCHES (default 0), CPILOT_CAPACITY_WINDOW (20s),
      supervised `sleep 3600`, leaving only its checks, so job counts
      beyond the machine's process limit can still be measured (the
      sleeps are idle; the row records which shape ran).
+     CPILOT_CAPACITY_SENSORS = native | exec (default unset): instead of
+     the stress shape, feed N gauges from N files (the arguments are
+     source counts, default 50) every CPILOT_CAPACITY_SENSOR_MS (1000)
+     and report CPU seconds per 1000 samples of the daemon plus all its
+     descendants. native uses `telemetry.sensors`; exec is the only way
+     without them: one periodic job per source running a script that
+     reads the file and execs `containerpilot -putmetric`.
 """
 import json
 import os
+import re
+import stat
 import sys
 import tempfile
 import time
+import urllib.request
 
 sys.path.insert(0, os.getcwd())
-from containerpilot_amd import harness  # noqa: E402
+from containerpilot_amd import BINARY, harness  # noqa: E402
 from bench import stress_config, free_port, scrape, histogram_p99  # noqa: E402
 
 job_counts = [int(a) for a in sys.argv[1:]] or [100, 300, 500]
@@ -48,6 +58,105 @@ def cpu_seconds(pid, reactor_only=False):
         fields = f.read().rpartition(")")[2].split()
     return (int(fields[11]) + int(fields[12])) / TICKS_PER_SEC
 
+
+def tree_cpu_seconds(root):
+    """CPU time of `root` and every live descendant, each with the
+    children it has already reaped (cutime + cstime), so short-lived
+    grandchildren count once their parent has waited for them."""
+    children = {}
+    times = {}
+    for entry in os.listdir("/proc"):
+        if not entry.isdigit():
+            continue
+        try:
+            with open("/proc/%s/stat" % entry) as f:
+                fields = f.read().rpartition(")")[2].split()
+        except OSError:
+            continue  # exited while we were listing
+        children.setdefault(int(fields[1]), []).append(int(entry))
+        times[int(entry)] = sum(int(x) for x in fields[11:15])
+    total, todo = 0, [root]
+    while todo:
+        pid = todo.pop()
+        total += times.get(pid, 0)
+        todo.extend(children.get(pid, []))
+    return total / TICKS_PER_SEC
+
+
+def sensor_capacity(mode, sources, every_ms):
+    wd = tempfile.mkdtemp()
+    port = free_port()
+    socket_path = os.path.join(wd, "cp.socket")
+    config_path = os.path.join(wd, "containerpilot.json5")
+    metrics, sensors, jobs = [], [], []
+    for i in range(sources):
+        path = os.path.join(wd, "source-%03d" % i)
+        with open(path, "w") as f:
+            f.write("%d\n" % (1000 + i))
+        key = "cap_src_v%03d" % i
+        metrics.append({"namespace": "cap", "subsystem": "src",
+                        "name": "v%03d" % i, "type": "gauge", "help": "v"})
+        if mode == "native":
+            sensors.append({"name": "src-%03d" % i, "file": path,
+                            "interval": "%dms" % every_ms,
+                            "record": [{"metric": key}]})
+        else:
+            script = os.path.join(wd, "sensor-%03d.sh" % i)
+            with open(script, "w") as f:
+                f.write('#!/bin/sh\nexec %s -config %s -putmetric '
+                        '"%s=$(cat %s)"\n' % (BINARY, config_path, key, path))
+            os.chmod(script, os.stat(script).st_mode | stat.S_IXUSR)
+            jobs.append({"name": "sensor-%03d" % i, "exec": script,
+                         "when": {"interval": "%dms" % every_ms}})
+    telemetry = {"port": port, "interfaces": ["static:127.0.0.1"],
+                 "metrics": metrics}
+    if sensors:
+        telemetry["sensors"] = sensors
+    d = harness.Daemon(config_dict={
+        "consul": "localhost:79", "stopTimeout": 1,
+        "logging": {"level": "ERROR"}, "control": {"socket": socket_path},
+        "jobs": jobs, "telemetry": telemetry}, workdir=wd)
+    d.start()
+    d.wait_for_socket(timeout=60)
+
+    def samples():
+        url = "http://127.0.0.1:%d/metrics" % port
+        with urllib.request.urlopen(url, timeout=10) as resp:
+            text = resp.read().decode()
+        if mode == "native":
+            pattern = (r'^containerpilot_sensor_samples\{sensor="[^"]*",'
+                       r'result="ok"\} (\S+)$')
+        else:
+            pattern = (r'^containerpilot_control_http_requests\{code="200",'
+                       r'path="/v3/metric"\} (\S+)$')
+        return sum(float(v) for v in re.findall(pattern, text, re.M))
+
+    time.sleep(warmup)
+    n0, c0, t0 = samples(), tree_cpu_seconds(d.proc.pid), time.time()
+    time.sleep(window)
+    n1, c1, el = samples(), tree_cpu_seconds(d.proc.pid), time.time() - t0
+    print(json.dumps({
+        "sensors": mode,
+        "sources": sources,
+        "interval_ms": every_ms,
+        "window_sec": round(el, 2),
+        "samples": round(n1 - n0),
+        "samples_per_sec": round((n1 - n0) / el, 1),
+        "tree_cpu_sec": round(c1 - c0, 3),
+        "cpu_sec_per_1000_samples":
+            round(1000.0 * (c1 - c0) / (n1 - n0), 4) if n1 > n0 else None,
+    }), flush=True)
+    d.cleanup()
+
+
+sensors_mode = os.environ.get("CPILOT_CAPACITY_SENSORS")
+if sensors_mode:
+    if sensors_mode not in ("native", "exec"):
+        sys.exit("CPILOT_CAPACITY_SENSORS must be native or exec")
+    every = int(os.environ.get("CPILOT_CAPACITY_SENSOR_MS", "1000"))
+    for count in [int(a) for a in sys.argv[1:]] or [50]:
+        sensor_capacity(sensors_mode, count, every)
+    sys.exit(0)
 
 for jobs in job_counts:
     wd = tempfile.mkdtemp()
