@@ -31,26 +31,28 @@ tsan:
 	  -DCPILOT_BIN_IN_TREE=OFF \
 	  -DCMAKE_CXX_FLAGS="-fsanitize=thread -g -O1"
 	ninja -C build-tsan cpilot_unittests cpilot_probetests \
-	  cpilot_rendertests cpilot_sensortests containerpilot \
-	  cpilot-spawn-helper
+	  cpilot_rendertests cpilot_sensortests cpilot_signaltests \
+	  containerpilot cpilot-spawn-helper
 	CPILOT_SPAWN_HELPER=build-tsan/bin/cpilot-spawn-helper \
 	  ./build-tsan/bin/cpilot_unittests
 	./build-tsan/bin/cpilot_probetests
 	./build-tsan/bin/cpilot_rendertests
 	./build-tsan/bin/cpilot_sensortests
+	./build-tsan/bin/cpilot_signaltests
 
 asan:
 	cmake -S . -B build-asan -G Ninja -DCMAKE_BUILD_TYPE=RelWithDebInfo \
 	  -DCPILOT_BIN_IN_TREE=OFF \
 	  -DCMAKE_CXX_FLAGS="-fsanitize=address,undefined -g -O1"
 	ninja -C build-asan cpilot_unittests cpilot_probetests \
-	  cpilot_rendertests cpilot_sensortests containerpilot \
-	  cpilot-spawn-helper
+	  cpilot_rendertests cpilot_sensortests cpilot_signaltests \
+	  containerpilot cpilot-spawn-helper
 	CPILOT_SPAWN_HELPER=build-asan/bin/cpilot-spawn-helper \
 	  ./build-asan/bin/cpilot_unittests
 	./build-asan/bin/cpilot_probetests
 	./build-asan/bin/cpilot_rendertests
 	./build-asan/bin/cpilot_sensortests
+	./build-asan/bin/cpilot_signaltests
 
 soak: build
 	python3 scripts/soak.py 300

@@ -52,6 +52,9 @@ def _load():
             ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p,
             ctypes.POINTER(ctypes.c_double),
             ctypes.POINTER(ctypes.c_void_p)]
+        _lib.cp_signal_number.restype = ctypes.c_int
+        _lib.cp_signal_number.argtypes = [
+            ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
         _lib.cp_free.argtypes = [ctypes.c_void_p]
     return _lib
 
@@ -153,6 +156,18 @@ def sensor_extract(body, record_json):
         lib.cp_free(err.value)
         raise ValueError(reason)
     return value.value
+
+
+def signal_number(name):
+    """The number of a signal that `jobs[].signal.send`, POST /v3/signal and
+    `-signal` accept ("SIGHUP" or "HUP"). Raises ValueError, listing the
+    accepted names, for any other name."""
+    lib = _load()
+    err = ctypes.c_void_p()
+    signo = lib.cp_signal_number(name.encode(), ctypes.byref(err))
+    if signo < 0:
+        raise ValueError(_take_string(lib, err.value))
+    return signo
 
 
 def watch_render(template_text, health_body_json, name, tag="", dc=""):

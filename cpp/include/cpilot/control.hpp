@@ -1,6 +1,7 @@
 // Control plane: HTTP server over a unix domain socket with the reference's
 // five POST endpoints + GET ping, implementing the code's actual behavior
-// (empty 200 body "\n", 422 on bad input, 405 on wrong method).
+// (empty 200 body "\n", 422 on bad input, 405 on wrong method), plus
+// POST /v3/signal (extension: signal a supervised job's process).
 // Parity: /root/reference/control/{control,config,endpoints}.go.
 #pragma once
 
@@ -8,6 +9,7 @@
 #include <memory>
 #include <string>
 
+#include "cpilot/command.hpp"
 #include "cpilot/events.hpp"
 #include "cpilot/http.hpp"
 #include "cpilot/json.hpp"
@@ -39,7 +41,16 @@ class ControlServer {
 
   const std::string& socketPath() const { return socketPath_; }
 
+  // POST /v3/signal resolves job names through this callback, which the
+  // App answers from the current generation's jobs. Returns false for an
+  // unknown job; *exec stays null for a job without an `exec`.
+  using JobLookup =
+      std::function<bool(const std::string& job, CommandPtr* exec)>;
+  void setJobLookup(JobLookup lookup) { jobLookup_ = std::move(lookup); }
+
  private:
+  int postSignal(const std::string& body);
+
   http::Response handle(const http::Request& req);
 
   Loop& loop_;
@@ -47,6 +58,7 @@ class ControlServer {
   std::shared_ptr<Bus> bus_;
   std::unique_ptr<http::Server> server_;
   std::shared_ptr<prom::Family> requestCounter_;
+  JobLookup jobLookup_;
 };
 
 }  // namespace cpilot

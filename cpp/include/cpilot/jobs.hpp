@@ -22,6 +22,7 @@
 #include "cpilot/events.hpp"
 #include "cpilot/json.hpp"
 #include "cpilot/probe.hpp"
+#include "cpilot/signals.hpp"
 #include "cpilot/timing.hpp"
 
 namespace cpilot {
@@ -41,9 +42,19 @@ enum class JobStatus {
 // (jobs/status.go:17-34)
 const char* jobStatusString(JobStatus s);
 
+// A job whose action is a signal to another job's process (`signal`,
+// exclusive with `exec`). `target` is the target job's Command, wired by
+// newJobConfigs once every job is parsed; it belongs to the same config
+// generation, so a reloaded config signals the reloaded process.
+struct SignalAction {
+  signals::Spec spec;
+  CommandPtr target;
+};
+
 struct JobConfig {
   std::string name;
   CommandPtr exec;
+  std::shared_ptr<SignalAction> signal;
 
   // service discovery
   int port = 0;
@@ -128,6 +139,11 @@ class Job : public Subscriber, public std::enable_shared_from_this<Job> {
   HandleResult onStartEvent();
   bool restartPermitted() const;
   void startJobExec();
+  // signal jobs: deliver on the reactor, then publish the exit event an
+  // exec that finished at once would have produced
+  void runSignalAction();
+  void endSignalWait(bool targetExited);
+  bool ignoredDuringSignalWait() const;
   void setStatus(JobStatus s);
   void checkRegistration();
   void sendHeartbeat();
@@ -142,6 +158,9 @@ class Job : public Subscriber, public std::enable_shared_from_this<Job> {
       stoppingTimeoutSource_;
   size_t hName_ = 0, hHeartbeat_ = 0, hRunEvery_ = 0, hCheck_ = 0;
   CommandPtr exec_;
+  std::shared_ptr<SignalAction> signal_;
+  size_t hSignalTarget_ = 0;
+  bool signalWaiting_ = false;  // delivered, `wait` pending
   JobStatus status_ = JobStatus::Idle;
   std::shared_ptr<ServiceDefinition> service_;
   CommandPtr healthCheckExec_;
@@ -167,7 +186,7 @@ class Job : public Subscriber, public std::enable_shared_from_this<Job> {
   std::shared_ptr<Bus> bus_;
   std::function<void()> completedCb_;
   uint64_t freqTimer_ = 0, heartbeatTimer_ = 0, startTimeoutTimer_ = 0,
-           stoppingTimer_ = 0, regRetryTimer_ = 0;
+           stoppingTimer_ = 0, regRetryTimer_ = 0, signalWaitTimer_ = 0;
 };
 
 }  // namespace cpilot

@@ -132,6 +132,16 @@ void App::startGeneration() {
   cfg_->discovery->start(loop_);
 
   control_ = std::make_unique<ControlServer>(loop_, cfg_->control.socketPath);
+  // read cfg_ at request time: always the current generation's jobs
+  control_->setJobLookup([this](const std::string& job, CommandPtr* exec) {
+    for (auto& jobCfg : cfg_->jobs) {
+      if (jobCfg->name == job) {
+        *exec = jobCfg->exec;
+        return true;
+      }
+    }
+    return false;
+  });
   std::string err;
   if (!control_->start(bus_, &err)) {
     logging::logf(logging::Level::Fatal, "%s", err.c_str());

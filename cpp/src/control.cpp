@@ -8,6 +8,7 @@
 #include "cpilot/command.hpp"
 #include "cpilot/decode.hpp"
 #include "cpilot/log.hpp"
+#include "cpilot/signals.hpp"
 
 namespace cpilot {
 
@@ -121,7 +122,8 @@ http::Response ControlServer::handle(const http::Request& req) {
   };
 
   if (path != "/v3/environ" && path != "/v3/reload" && path != "/v3/metric" &&
-      path != "/v3/maintenance/enable" && path != "/v3/maintenance/disable") {
+      path != "/v3/signal" && path != "/v3/maintenance/enable" &&
+      path != "/v3/maintenance/disable") {
     http::Response notFound;
     notFound.status = 404;
     notFound.body = "404 page not found\n";
@@ -166,6 +168,7 @@ http::Response ControlServer::handle(const http::Request& req) {
     }
     return finish(200);
   }
+  if (path == "/v3/signal") return finish(postSignal(req.body));
   if (path == "/v3/maintenance/enable") {
     bus_->publish(GlobalEnterMaintenance);
     return finish(200);
@@ -175,6 +178,48 @@ http::Response ControlServer::handle(const http::Request& req) {
     return finish(200);
   }
   return finish(404);
+}
+
+// PostSignal (extension): {"<job>": "<signal>", ...}. Everything is
+// validated before anything is sent, so a 422 means no process was
+// signalled; then every entry is delivered in order, to the process and
+// not its group, and a target without a running process makes it a 409.
+int ControlServer::postSignal(const std::string& body) {
+  struct Target {
+    std::string job, sigName;
+    CommandPtr exec;
+    int signo = 0;
+  };
+  std::vector<Target> targets;
+  try {
+    Json doc = parseJson5(body);
+    if (!doc.isObject()) return 422;
+    for (auto& kv : doc.object()) {
+      Target t;
+      t.job = kv.first;
+      if (!kv.second.isString() ||
+          !signals::fromName(kv.second.str(), &t.signo, &t.sigName))
+        return 422;
+      if (!jobLookup_ || !jobLookup_(t.job, &t.exec) || !t.exec) return 422;
+      targets.push_back(std::move(t));
+    }
+  } catch (const std::exception&) {
+    return 422;
+  }
+  int status = 200;
+  for (auto& t : targets) {
+    pid_t pid = t.exec->pid();
+    std::string reason;
+    if (signals::deliver(pid, t.signo, /*group=*/false, &reason)) {
+      LOG_INFO("control: sent %s to job %s at pid %d", t.sigName.c_str(),
+               t.job.c_str(), (int)pid);
+    } else {
+      LOG_WARN("control: %s not sent to job %s: %s", t.sigName.c_str(),
+               t.job.c_str(), reason.c_str());
+      status = 409;
+    }
+  }
+  return status;
 }
 
 }  // namespace cpilot

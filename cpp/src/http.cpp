@@ -28,6 +28,7 @@ const char* statusText(int code) {
     case 400: return "Bad Request";
     case 404: return "Not Found";
     case 405: return "Method Not Allowed";
+    case 409: return "Conflict";
     case 411: return "Length Required";
     case 413: return "Payload Too Large";
     case 422: return "Unprocessable Entity";

@@ -447,6 +447,54 @@ bool validateExec(const Json& raw, std::shared_ptr<JobConfig>& cfg,
   return true;
 }
 
+// signal{} block: a job whose action is a signal to another job's process.
+// The target name is resolved by newJobConfigs once all jobs are parsed.
+bool validateSignal(const Json& raw, std::shared_ptr<JobConfig>& cfg,
+                    std::string* err) {
+  const Json* sig = raw.find("signal");
+  if (!sig || sig->isNull()) return true;
+  auto given = [&](const char* key) {
+    const Json* v = raw.find(key);
+    return v && !v->isNull();
+  };
+  if (given("exec")) {
+    *err = "job[" + cfg->name + "].signal cannot be combined with 'exec'";
+    return false;
+  }
+  // no child, no output and nothing to register
+  for (const char* key : {"port", "health", "timeout", "logging"}) {
+    if (given(key)) {
+      *err = "job[" + cfg->name + "].signal cannot be combined with '" + key +
+             "': a signal job starts no process";
+      return false;
+    }
+  }
+  auto action = std::make_shared<SignalAction>();
+  std::string key, specErr;
+  if (!signals::parseSpec(*sig, &action->spec, &key, &specErr)) {
+    *err = "job[" + cfg->name + "].signal" + key + (key.empty() ? ": " : " ") +
+           specErr;
+    return false;
+  }
+  cfg->signal = action;
+  return true;
+}
+
+// a restart of an action that finishes at once is a busy loop: only
+// `when.interval` paces it (call after validateWhen and validateRestarts)
+bool validateSignalRestarts(const Json* restarts,
+                            const std::shared_ptr<JobConfig>& cfg,
+                            std::string* err) {
+  if (!cfg->signal || cfg->freqInterval > Duration(0) ||
+      cfg->restartLimit == 0)
+    return true;
+  std::string rendered =
+      restarts->isString() ? restarts->str() : restarts->dump();
+  *err = "job[" + cfg->name + "].signal cannot be combined with restarts '" +
+         rendered + "' unless 'when.interval' is set";
+  return false;
+}
+
 }  // namespace
 
 bool validateJobConfig(const Json& raw, ConsulBackend* disc,
@@ -459,7 +507,7 @@ bool validateJobConfig(const Json& raw, ConsulBackend* disc,
           raw,
           {"name", "exec", "port", "initial_status", "interfaces", "tags",
            "consul", "health", "timeout", "restarts", "stopTimeout", "when",
-           "logging"},
+           "logging", "signal"},
           err)) {
     *err = "job configuration error: " + *err;
     return false;
@@ -492,6 +540,7 @@ bool validateJobConfig(const Json& raw, ConsulBackend* disc,
     }
   }
 
+  if (!validateSignal(raw, cfg, err)) return false;
   // order mirrors Config.Validate (jobs/config.go:118-133)
   if (!validateDiscovery(raw, disc, cfg, err)) return false;
   if (!validateWhen(raw.find("when"), cfg, err)) return false;
@@ -509,6 +558,7 @@ bool validateJobConfig(const Json& raw, ConsulBackend* disc,
   cfg->stoppingWaitEvent = NonEvent;
   if (!validateRestarts(raw.find("restarts"), raw.find("when"), cfg, err))
     return false;
+  if (!validateSignalRestarts(raw.find("restarts"), cfg, err)) return false;
   if (!validateExec(raw, cfg, err)) return false;
   *out = cfg;
   return true;
@@ -538,6 +588,32 @@ bool newJobConfigs(const Json& rawJobs, ConsulBackend* disc,
         cfg->stoppingWaitEvent = Event{EventCode::Stopped, dep.second};
     }
   }
+  // wire signal jobs to their target's Command
+  for (auto& cfg : *out) {
+    if (!cfg->signal) continue;
+    const std::string& target = cfg->signal->spec.job;
+    std::string where = "job[" + cfg->name + "].signal.job '" + target + "' ";
+    if (target == cfg->name) {
+      *err = where + "is the job itself";
+      return false;
+    }
+    const JobConfig* found = nullptr;
+    for (auto& other : *out) {
+      if (other->name == target) {
+        found = other.get();
+        break;
+      }
+    }
+    if (!found) {
+      *err = where + "is not a job in this config";
+      return false;
+    }
+    if (!found->exec) {
+      *err = where + "has no 'exec' to signal";
+      return false;
+    }
+    cfg->signal->target = found->exec;
+  }
   return true;
 }
 
@@ -546,6 +622,7 @@ bool newJobConfigs(const Json& rawJobs, ConsulBackend* disc,
 Job::Job(const std::shared_ptr<JobConfig>& cfg)
     : name_(cfg->name),
       exec_(cfg->exec),
+      signal_(cfg->signal),
       service_(cfg->serviceDefinition),
       healthCheckExec_(cfg->healthCheckExec),
       healthProbe_(cfg->healthProbe),
@@ -568,6 +645,7 @@ Job::Job(const std::shared_ptr<JobConfig>& cfg)
   hHeartbeat_ = h(heartbeatSource_);
   hRunEvery_ = h(runEverySource_);
   hCheck_ = h(healthCheckName_);
+  if (signal_) hSignalTarget_ = h(signal_->spec.job);
   if (name_ == "containerpilot") {
     // hardcoded always-healthy telemetry job (jobs/jobs.go:82-87)
     status_ = JobStatus::AlwaysHealthy;
@@ -583,6 +661,9 @@ Subscription Job::subscription() const {
   if (!startEvent_.source.empty()) sub.sources.push_back(startEvent_.source);
   if (stoppingWaitEvent_ != NonEvent)
     sub.sources.push_back(stoppingWaitEvent_.source);
+  // a pending `wait` ends on the target's exit events
+  if (signal_ && signal_->spec.wait > Duration(0))
+    sub.sources.push_back(signal_->spec.job);
   sub.codes = {EventCode::Quit, EventCode::Shutdown,
                EventCode::EnterMaintenance, EventCode::ExitMaintenance,
                EventCode::Signal};
@@ -706,10 +787,14 @@ Job::HandleResult Job::dispatch(const Event& event, size_t srcHash) {
     case EventCode::ExitFailed:
       if (srcIs(hCheck_, healthCheckName_)) return onHealthCheckFailed();
       if (srcIs(hName_, name_)) return onExecExit();
+      if (signalWaiting_ && srcIs(hSignalTarget_, signal_->spec.job))
+        endSignalWait(true);
       break;
     case EventCode::ExitSuccess:
       if (srcIs(hCheck_, healthCheckName_)) return onHealthCheckPassed();
       if (srcIs(hName_, name_)) return onExecExit();
+      if (signalWaiting_ && srcIs(hSignalTarget_, signal_->spec.job))
+        endSignalWait(true);
       break;
     case EventCode::Quit:
       if (srcIs(hName_, name_)) return onQuit();
@@ -742,6 +827,53 @@ void Job::startJobExec() {
   }
   setStatus(JobStatus::Unknown);
   if (exec_) exec_->run(*loop_, bus_);
+  else if (signal_) runSignalAction();
+}
+
+void Job::runSignalAction() {
+  const signals::Spec& spec = signal_->spec;
+  if (ignoredDuringSignalWait()) return;  // a `when.source: "SIGHUP"` start
+  // a target whose launch is still in flight has no pid yet
+  pid_t pid = signal_->target ? signal_->target->pid() : -1;
+  std::string reason;
+  if (!signals::deliver(pid, spec.signo, spec.group, &reason)) {
+    if (pid <= 0) reason = "job '" + spec.job + "' has " + reason;
+    reason = name_ + ": " + spec.name + " not sent: " + reason;
+    LOG_WARN("%s", reason.c_str());
+    bus_->publish(Event{EventCode::ExitFailed, name_});
+    bus_->publish(Event{EventCode::Error, reason});
+    return;
+  }
+  LOG_INFO("%s: sent %s to job %s at pid %d%s", name_.c_str(),
+           spec.name.c_str(), spec.job.c_str(), (int)pid,
+           spec.group ? " (process group)" : "");
+  if (spec.wait <= Duration(0)) {
+    bus_->publish(Event{EventCode::ExitSuccess, name_});
+    return;
+  }
+  signalWaiting_ = true;
+  auto self = shared_from_this();
+  signalWaitTimer_ = loop_->addTimeout(spec.wait, [this, self] {
+    signalWaitTimer_ = 0;
+    endSignalWait(false);
+  });
+}
+
+// the target exited (how does not matter), or `wait` ran out: nothing is
+// killed, the job just reports which of the two happened
+void Job::endSignalWait(bool targetExited) {
+  signalWaiting_ = false;
+  if (signalWaitTimer_) {
+    loop_->cancelTimer(signalWaitTimer_);
+    signalWaitTimer_ = 0;
+  }
+  if (targetExited) {
+    bus_->publish(Event{EventCode::ExitSuccess, name_});
+    return;
+  }
+  LOG_WARN("%s: job %s still running after the wait", name_.c_str(),
+           signal_->spec.job.c_str());
+  bus_->publish(Event{EventCode::ExitFailed, name_});
 }
 
 Job::HandleResult Job::onHeartbeatTimerExpired() {
@@ -777,7 +909,17 @@ Job::HandleResult Job::onStartTimeoutExpired() {
   return kContinue;
 }
 
+// A start that arrives while a signal job's `wait` is pending is ignored
+// before it can use up a start or a restart.
+bool Job::ignoredDuringSignalWait() const {
+  if (!signalWaiting_) return false;
+  LOG_DEBUG("%s: start ignored, still waiting for %s to exit", name_.c_str(),
+            signal_->spec.job.c_str());
+  return true;
+}
+
 Job::HandleResult Job::onRunEveryTimerExpired() {
+  if (ignoredDuringSignalWait()) return kContinue;
   if (!restartPermitted()) {
     LOG_DEBUG("interval expired but restart not permitted: %s", name_.c_str());
     startEvent_ = NonEvent;
@@ -809,7 +951,7 @@ Job::HandleResult Job::onQuit() {
   restartsRemain_ = 0;
   if ((startEvent_.code == EventCode::Stopping ||
        startEvent_.code == EventCode::Stopped) &&
-      exec_) {
+      (exec_ || signal_)) {
     // pre-stop / post-stop jobs get one more start (jobs/jobs.go:295-308)
     if (startsRemain_ == kUnlimited) startsRemain_ = 1;
     return kContinue;
@@ -853,6 +995,7 @@ Job::HandleResult Job::onSignalEvent(const std::string& sig) {
 }
 
 Job::HandleResult Job::onStartEvent() {
+  if (ignoredDuringSignalWait()) return kContinue;
   if (startsRemain_ == 0) {
     startEvent_ = NonEvent;
     return kHalt;
@@ -912,8 +1055,10 @@ void Job::finishCleanup() {
   if (startTimeoutTimer_) loop_->cancelTimer(startTimeoutTimer_);
   if (stoppingTimer_) loop_->cancelTimer(stoppingTimer_);
   if (regRetryTimer_) loop_->cancelTimer(regRetryTimer_);
+  if (signalWaitTimer_) loop_->cancelTimer(signalWaitTimer_);
   freqTimer_ = heartbeatTimer_ = startTimeoutTimer_ = stoppingTimer_ =
-      regRetryTimer_ = 0;
+      regRetryTimer_ = signalWaitTimer_ = 0;
+  signalWaiting_ = false;
   if (exec_ && exec_->running()) exec_->term();
   if (healthCheckExec_ && healthCheckExec_->running()) healthCheckExec_->term();
   if (healthProbe_ && healthProbe_->running()) healthProbe_->cancel();

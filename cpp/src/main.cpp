@@ -33,6 +33,7 @@ struct Flags {
   std::string maintenance;
   std::map<std::string, std::string> putMetrics;
   std::map<std::string, std::string> putEnv;
+  std::map<std::string, std::string> signals;  // -signal job=SIG (extension)
   // extensions beyond the reference CLI:
   std::string statsOut;   // -stats-out <file>: write bus stats JSON on exit
   int benchSeconds = 0;   // -bench-seconds N: shut down after N seconds
@@ -53,6 +54,7 @@ struct Flags {
           "  -putenv value\n        Update environ: 'key=value'\n"
           "  -putmetric value\n        Update metrics: 'key=value'\n"
           "  -reload\n        Reload a running ContainerPilot process.\n"
+          "  -signal value\n        Signal a job's process: 'job=SIGHUP'\n"
           "  -template\n        Render template and quit.\n"
           "  -version\n        Show version identifier and quit.\n");
   exit(2);
@@ -92,6 +94,8 @@ bool parseFlags(int argc, char** argv, Flags* f) {
       if (!parseKV(next("-putmetric"), &f->putMetrics)) return false;
     } else if (arg == "-putenv") {
       if (!parseKV(next("-putenv"), &f->putEnv)) return false;
+    } else if (arg == "-signal") {
+      if (!parseKV(next("-signal"), &f->signals)) return false;
     } else if (arg == "-stats-out") f->statsOut = next("-stats-out");
     else if (arg == "-bench-seconds")
       f->benchSeconds = atoi(next("-bench-seconds").c_str());
@@ -189,6 +193,9 @@ int main(int argc, char** argv) {
   if (!flags.putMetrics.empty())
     return controlPost(flags.config, "/v3/metric", mapToJson(flags.putMetrics),
                        "-putmetric");
+  if (!flags.signals.empty())
+    return controlPost(flags.config, "/v3/signal", mapToJson(flags.signals),
+                       "-signal");
   if (flags.ping) {
     std::string socketPath, err;
     if (!initSocket(flags.config, &socketPath, &err)) {

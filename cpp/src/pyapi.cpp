@@ -10,6 +10,7 @@
 #include "cpilot/discovery.hpp"
 #include "cpilot/json.hpp"
 #include "cpilot/sensor.hpp"
+#include "cpilot/signals.hpp"
 #include "cpilot/timing.hpp"
 #include "cpilot/tmpl.hpp"
 #include "cpilot/version.hpp"
@@ -171,6 +172,19 @@ int cp_sensor_extract(const char* body, size_t bodyLen, const char* recordJson,
     if (errOut) *errOut = dupString(e.what());
     return 0;
   }
+}
+
+// The number of a signal that `jobs[].signal.send`, POST /v3/signal and
+// `-signal` accept, or -1 for a refused name (*errOut lists the accepted
+// names).
+int cp_signal_number(const char* name, char** errOut) {
+  int signo = 0;
+  if (signals::fromName(name, &signo, nullptr)) return signo;
+  if (errOut)
+    *errOut = dupString(std::string("'") + name +
+                        "' is not accepted: must be one of " +
+                        signals::acceptedNames());
+  return -1;
 }
 
 }  // extern "C"

@@ -20,6 +20,13 @@ Env: CPILOT_CAPACITY_WATCHES (default 0), CPILOT_CAPACITY_WINDOW (20s),
      descendants. native uses `telemetry.sensors`; exec is the only way
      without them: one periodic job per source running a script that
      reads the file and execs `containerpilot -putmetric`.
+     CPILOT_CAPACITY_SIGNALS = native | exec (default unset): instead of
+     the stress shape, N periodic jobs (the arguments are job counts,
+     default 10) each send SIGHUP to one supervised target every
+     CPILOT_CAPACITY_SIGNAL_MS (100); reports CPU seconds per 1000
+     deliveries of the daemon plus all its descendants. native uses
+     `jobs[].signal`; exec is the only way without it: a job running
+     `/bin/sh -c 'kill -HUP $CONTAINERPILOT_NGINX_PID'`.
 """
 import json
 import os
@@ -148,6 +155,66 @@ def sensor_capacity(mode, sources, every_ms):
     }), flush=True)
     d.cleanup()
 
+
+def signal_capacity(mode, count, every_ms):
+    wd = tempfile.mkdtemp()
+    port = free_port()
+    # the target handles SIGHUP and otherwise idles: its cost is the same
+    # in both modes
+    jobs = [{"name": "nginx",
+             "exec": ["/bin/sh", "-c",
+                      "trap : HUP; while :; do sleep 1; done"]}]
+    for i in range(count):
+        job = {"name": "reload-%03d" % i,
+               "when": {"interval": "%dms" % every_ms}}
+        if mode == "native":
+            job["signal"] = {"job": "nginx", "send": "SIGHUP"}
+        else:
+            job["exec"] = ["/bin/sh", "-c",
+                           "kill -HUP $CONTAINERPILOT_NGINX_PID"]
+        jobs.append(job)
+    d = harness.Daemon(config_dict={
+        "consul": "localhost:79", "stopTimeout": 1,
+        "logging": {"level": "ERROR"}, "jobs": jobs,
+        "telemetry": {"port": port, "interfaces": ["static:127.0.0.1"]}},
+        workdir=wd)
+    d.start()
+    d.wait_for_socket(timeout=60)
+
+    def deliveries():
+        url = "http://127.0.0.1:%d/metrics" % port
+        with urllib.request.urlopen(url, timeout=10) as resp:
+            text = resp.read().decode()
+        pattern = (r'^containerpilot_events\{code="ExitSuccess",'
+                   r'source="reload-\d+"\} (\S+)$')
+        return sum(float(v) for v in re.findall(pattern, text, re.M))
+
+    time.sleep(warmup)
+    n0, c0, t0 = deliveries(), tree_cpu_seconds(d.proc.pid), time.time()
+    time.sleep(window)
+    n1, c1, el = deliveries(), tree_cpu_seconds(d.proc.pid), time.time() - t0
+    print(json.dumps({
+        "signals": mode,
+        "jobs": count,
+        "interval_ms": every_ms,
+        "window_sec": round(el, 2),
+        "deliveries": round(n1 - n0),
+        "deliveries_per_sec": round((n1 - n0) / el, 1),
+        "tree_cpu_sec": round(c1 - c0, 3),
+        "cpu_sec_per_1000_deliveries":
+            round(1000.0 * (c1 - c0) / (n1 - n0), 4) if n1 > n0 else None,
+    }), flush=True)
+    d.cleanup()
+
+
+signals_mode = os.environ.get("CPILOT_CAPACITY_SIGNALS")
+if signals_mode:
+    if signals_mode not in ("native", "exec"):
+        sys.exit("CPILOT_CAPACITY_SIGNALS must be native or exec")
+    every = int(os.environ.get("CPILOT_CAPACITY_SIGNAL_MS", "100"))
+    for count in [int(a) for a in sys.argv[1:]] or [10]:
+        signal_capacity(signals_mode, count, every)
+    sys.exit(0)
 
 sensors_mode = os.environ.get("CPILOT_CAPACITY_SENSORS")
 if sensors_mode:
