@@ -11,6 +11,7 @@ build:
 
 unit: build
 	./bin/cpilot_unittests
+	./bin/cpilot_metricstests tests/golden/metrics_cases.json
 
 integration: build
 	python3 -m pytest tests/ -q -m "not gpu"
@@ -32,13 +33,14 @@ tsan:
 	  -DCMAKE_CXX_FLAGS="-fsanitize=thread -g -O1"
 	ninja -C build-tsan cpilot_unittests cpilot_probetests \
 	  cpilot_rendertests cpilot_sensortests cpilot_signaltests \
-	  containerpilot cpilot-spawn-helper
+	  cpilot_metricstests containerpilot cpilot-spawn-helper
 	CPILOT_SPAWN_HELPER=build-tsan/bin/cpilot-spawn-helper \
 	  ./build-tsan/bin/cpilot_unittests
 	./build-tsan/bin/cpilot_probetests
 	./build-tsan/bin/cpilot_rendertests
 	./build-tsan/bin/cpilot_sensortests
 	./build-tsan/bin/cpilot_signaltests
+	./build-tsan/bin/cpilot_metricstests tests/golden/metrics_cases.json
 
 asan:
 	cmake -S . -B build-asan -G Ninja -DCMAKE_BUILD_TYPE=RelWithDebInfo \
@@ -46,13 +48,14 @@ asan:
 	  -DCMAKE_CXX_FLAGS="-fsanitize=address,undefined -g -O1"
 	ninja -C build-asan cpilot_unittests cpilot_probetests \
 	  cpilot_rendertests cpilot_sensortests cpilot_signaltests \
-	  containerpilot cpilot-spawn-helper
+	  cpilot_metricstests containerpilot cpilot-spawn-helper
 	CPILOT_SPAWN_HELPER=build-asan/bin/cpilot-spawn-helper \
 	  ./build-asan/bin/cpilot_unittests
 	./build-asan/bin/cpilot_probetests
 	./build-asan/bin/cpilot_rendertests
 	./build-asan/bin/cpilot_sensortests
 	./build-asan/bin/cpilot_signaltests
+	./build-asan/bin/cpilot_metricstests tests/golden/metrics_cases.json
 
 soak: build
 	python3 scripts/soak.py 300

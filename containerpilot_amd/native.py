@@ -55,6 +55,12 @@ def _load():
         _lib.cp_signal_number.restype = ctypes.c_int
         _lib.cp_signal_number.argtypes = [
             ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
+        _lib.cp_metrics_replay.restype = ctypes.c_void_p
+        _lib.cp_metrics_replay.argtypes = [
+            ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
+        _lib.cp_metric_value_string.restype = ctypes.c_void_p
+        _lib.cp_metric_value_string.argtypes = [
+            ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
         _lib.cp_free.argtypes = [ctypes.c_void_p]
     return _lib
 
@@ -179,6 +185,33 @@ def watch_render(template_text, health_body_json, name, tag="", dc=""):
     out = lib.cp_watch_render(template_text.encode(),
                               health_body_json.encode(), name.encode(),
                               tag.encode(), dc.encode(), ctypes.byref(err))
+    if not out:
+        raise ValueError(_take_string(lib, err.value))
+    return _take_string(lib, out)
+
+
+def metrics_replay(script_json):
+    """Replay a script against the daemon's own metrics path in a registry
+    of its own and return the /metrics text. The script (JSON text) has
+    `metrics` (entries as in `telemetry.metrics`) with `events` (a list of
+    "name|value" strings, each offered to every metric as the bus would),
+    and for the internal-collector path `families` ({name, help, type,
+    labels, buckets}) with `ops` ({family, op: inc | set | observe |
+    setBuckets, labels, value, bounds}). Raises ValueError with the config
+    error of a refused metric, or on a malformed script."""
+    lib = _load()
+    err = ctypes.c_void_p()
+    out = lib.cp_metrics_replay(script_json.encode(), ctypes.byref(err))
+    if not out:
+        raise ValueError(_take_string(lib, err.value))
+    return _take_string(lib, out)
+
+
+def metric_value_string(json_text):
+    """The value text `POST /v3/metric` records for one JSON value."""
+    lib = _load()
+    err = ctypes.c_void_p()
+    out = lib.cp_metric_value_string(json_text.encode(), ctypes.byref(err))
     if not out:
         raise ValueError(_take_string(lib, err.value))
     return _take_string(lib, out)

@@ -25,6 +25,11 @@ struct ControlConfig {
 
 bool newControlConfig(const Json* raw, ControlConfig* out, std::string* err);
 
+// The value text POST /v3/metric puts after "name|" for one JSON value
+// (Go's fmt %v of the unmarshaled interface{}, endpoints.go:124-127): a
+// number is spelled so that Metric::record reads back every bit of it.
+std::string metricValueString(const Json& v);
+
 class ControlServer {
  public:
   // reloadCb: invoked by POST /v3/reload after setting the bus reload flag

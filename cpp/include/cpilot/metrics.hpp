@@ -6,6 +6,8 @@
 #pragma once
 
 #include <algorithm>
+#include <cmath>
+#include <cstdint>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -24,9 +26,15 @@ struct HistogramData {
   uint64_t count = 0;
   double sum = 0;
   HistogramData() : counts(bounds.size(), 0) {}
+  // Unchanged bounds keep every count (a config reload sets the same
+  // bounds again); new bounds start the histogram over, count and sum
+  // included, so the buckets never fall behind +Inf.
   void setBounds(std::vector<double> b) {
+    if (b == bounds) return;
     bounds = std::move(b);
     counts.assign(bounds.size(), 0);
+    count = 0;
+    sum = 0;
   }
   void observe(double v) {
     for (size_t i = 0; i < bounds.size(); i++)
@@ -49,12 +57,16 @@ struct SummaryData {
     count++;
     sum += v;
   }
-  double quantile(double q) const {
-    if (window.empty()) return 0;
+  // Nearest rank: the ceil(q*m)-th smallest of the m samples in the
+  // window, q = num/den in integers. NaN without a sample, as the Go client
+  // exposes. The window never holds NaN (Family::observe refuses it).
+  double quantile(uint64_t num, uint64_t den) const {
+    if (window.empty()) return std::nan("");
     std::vector<double> s(window);
-    std::sort(s.begin(), s.end());
-    size_t idx = (size_t)(q * (s.size() - 1));
-    return s[idx];
+    uint64_t rank = (num * s.size() + den - 1) / den;
+    if (rank < 1) rank = 1;
+    std::nth_element(s.begin(), s.begin() + (rank - 1), s.end());
+    return s[rank - 1];
   }
 };
 
@@ -74,23 +86,31 @@ class Family {
         type_(type),
         labelNames_(std::move(labelNames)) {}
 
-  void inc(const std::vector<std::string>& labels = {}, double by = 1) {
+  // A counter refuses a negative or NaN increment (false, unchanged).
+  bool inc(const std::vector<std::string>& labels = {}, double by = 1) {
+    if (type_ == MetricType::Counter && !(by >= 0)) return false;
     std::lock_guard<std::mutex> l(mu_);
     child(labels).value += by;
+    return true;
   }
   void set(const std::vector<std::string>& labels, double v) {
     std::lock_guard<std::mutex> l(mu_);
     child(labels).value = v;
   }
   void set(double v) { set({}, v); }
-  void observe(const std::vector<std::string>& labels, double v) {
+  // NaN is refused (false, unchanged): it would stay in the sum for good
+  // and has no rank among the samples.
+  bool observe(const std::vector<std::string>& labels, double v) {
+    if (std::isnan(v)) return false;
     std::lock_guard<std::mutex> l(mu_);
     Child& c = child(labels);
     if (type_ == MetricType::Histogram) c.hist.observe(v);
     else c.summ.observe(v);
+    return true;
   }
-  void observe(double v) { observe({}, v); }
-  // set histogram bucket bounds (before first observe)
+  bool observe(double v) { return observe({}, v); }
+  // set histogram bucket bounds; see HistogramData::setBounds for a family
+  // that already has observations
   void setBuckets(std::vector<double> bounds) {
     std::lock_guard<std::mutex> l(mu_);
     bucketBounds_ = bounds;
@@ -116,6 +136,17 @@ class Family {
   mutable std::mutex mu_;
   std::map<std::vector<std::string>, Child> children_;
 };
+
+// Shortest decimal text that strtod (and Go's ParseFloat) reads back as
+// exactly `v`: whole numbers below 1e15 as plain digits, otherwise %g's
+// spelling ("0.005", "1e-05", "2.5e+20"); "NaN", "+Inf", "-Inf".
+std::string formatValue(double v);
+
+// [a-zA-Z_:][a-zA-Z0-9_:]*
+bool validMetricName(const std::string& name);
+
+// The daemon's own families; a user metric may not take one of these names.
+bool isInternalName(const std::string& name);
 
 // Global registry (like prometheus.MustRegister / default registry)
 class Registry {

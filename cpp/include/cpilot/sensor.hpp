@@ -64,8 +64,9 @@ struct RecordSpec {
 bool parseRecord(const Json& raw, RecordSpec* out, std::string* errKey,
                  std::string* err);
 
-// The number under the rule of Metric::record (trim, strtod consumes all)
-// that is also finite.
+// A finite number in strtod's grammar, white space trimmed: sources write
+// hex and the like, and what is found here is published through
+// formatValue, whose text Metric::record always accepts.
 bool parseNumber(const std::string& token, double* out);
 
 // Extract the record's number from `body` and apply its scale. On failure
@@ -73,7 +74,8 @@ bool parseNumber(const std::string& token, double* out);
 bool extract(const std::string& body, const RecordSpec& rec, double* out,
              std::string* reason);
 
-// Shortest decimal text that strtod reads back as exactly `v`.
+// Shortest decimal text that strtod reads back as exactly `v`
+// (prom::formatValue).
 std::string formatValue(double v);
 
 // Read a regular file to EOF without ever blocking on a FIFO or a tty.

@@ -26,9 +26,20 @@ struct MetricConfig {
   std::shared_ptr<prom::Family> collector;
 };
 
+// Collectors register in `registry` (the global one by default). A joined
+// name Prometheus would refuse, or one of the daemon's own family names,
+// is a config error.
 bool newMetricConfigs(const Json& raw,
                       std::vector<std::shared_ptr<MetricConfig>>* out,
-                      std::string* err);
+                      std::string* err,
+                      prom::Registry* registry = nullptr);
+
+// The float a recorded value string stands for under the reference's rule
+// (strings.TrimSpace, then Go 1.9's strconv.ParseFloat): decimal digits
+// with an optional sign, point and exponent, or inf / infinity / nan in any
+// case, the sign on inf only. No hex, no underscores, no "nan(...)"; a
+// value too large for a double is refused, one too small is 0.
+bool parseMetricValue(const std::string& text, double* out);
 
 // Per-metric event subscriber: parses "name|value" Metric events and
 // records into its collector (telemetry/metrics.go:48-112).

@@ -88,22 +88,15 @@ http::Response plainResponse(int status) {
   return resp;
 }
 
-// render a JSON value the way Go fmt %v renders the unmarshaled
-// interface{} (endpoints.go:124-127): float64 integral values print
-// without decimals
+}  // namespace
+
 std::string metricValueString(const Json& v) {
   if (v.isString()) return v.str();
   if (v.isBool()) return v.boolean() ? "true" : "false";
   if (v.isInt()) return std::to_string(v.asInt());
-  if (v.isDouble()) {
-    char buf[40];
-    snprintf(buf, sizeof(buf), "%g", v.asDouble());
-    return buf;
-  }
+  if (v.isDouble()) return prom::formatValue(v.asDouble());
   return v.dump();
 }
-
-}  // namespace
 
 http::Response ControlServer::handle(const http::Request& req) {
   http::Response resp;

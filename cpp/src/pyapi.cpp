@@ -4,13 +4,18 @@
 // daemon runs.
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "cpilot/config.hpp"
+#include "cpilot/control.hpp"
 #include "cpilot/discovery.hpp"
 #include "cpilot/json.hpp"
 #include "cpilot/sensor.hpp"
 #include "cpilot/signals.hpp"
+#include "cpilot/telemetry.hpp"
 #include "cpilot/timing.hpp"
 #include "cpilot/tmpl.hpp"
 #include "cpilot/version.hpp"
@@ -185,6 +190,106 @@ int cp_signal_number(const char* name, char** errOut) {
                         "' is not accepted: must be one of " +
                         signals::acceptedNames());
   return -1;
+}
+
+// Replay a script against the daemon's own metrics path, in a registry of
+// its own, and return the exposition:
+//   {metrics:  [<telemetry.metrics entry>, ...],
+//    events:   ["name|value", ...],
+//    families: [{name, help, type, labels: [..], buckets: [..]}, ...],
+//    ops:      [{family, op: "inc"|"set"|"observe"|"setBuckets",
+//                labels: [..], value, bounds: [..]}, ...]}
+// `metrics` go through newMetricConfigs and every event through each
+// Metric::onEvent, in order; then `ops` run on the `families` (the
+// internal-collector path). Returns nullptr + *errOut on a config error or
+// a malformed script.
+char* cp_metrics_replay(const char* scriptJson, char** errOut) {
+  try {
+    Json script = parseJson5(scriptJson);
+    prom::Registry registry;
+    std::string err;
+    std::vector<std::shared_ptr<MetricConfig>> cfgs;
+    if (const Json* m = script.find("metrics")) {
+      if (!newMetricConfigs(*m, &cfgs, &err, &registry)) {
+        if (errOut) *errOut = dupString(err);
+        return nullptr;
+      }
+    }
+    std::vector<std::shared_ptr<Metric>> metrics;
+    for (auto& cfg : cfgs) metrics.push_back(std::make_shared<Metric>(cfg));
+    if (const Json* events = script.find("events")) {
+      for (auto& e : events->array())
+        for (auto& metric : metrics)
+          metric->onEvent(Event{EventCode::Metric, e.str()});
+    }
+
+    auto need = [](const Json& obj, const char* key) -> const Json& {
+      const Json* v = obj.find(key);
+      if (!v) throw std::runtime_error(std::string("script: missing ") + key);
+      return *v;
+    };
+    auto strings = [](const Json* v) {
+      std::vector<std::string> out;
+      if (v)
+        for (auto& s : v->array()) out.push_back(s.str());
+      return out;
+    };
+    auto doubles = [](const Json* v) {
+      std::vector<double> out;
+      if (v)
+        for (auto& d : v->array()) out.push_back(d.asDouble());
+      return out;
+    };
+    std::map<std::string, std::shared_ptr<prom::Family>> families;
+    if (const Json* fams = script.find("families")) {
+      for (auto& f : fams->array()) {
+        std::string name = need(f, "name").str();
+        std::string type = need(f, "type").str();
+        prom::MetricType mt;
+        if (type == "counter") mt = prom::MetricType::Counter;
+        else if (type == "gauge") mt = prom::MetricType::Gauge;
+        else if (type == "histogram") mt = prom::MetricType::Histogram;
+        else if (type == "summary") mt = prom::MetricType::Summary;
+        else throw std::runtime_error("invalid metric type: " + type);
+        const Json* help = f.find("help");
+        auto fam = registry.registerFamily(name, help ? help->str() : "", mt,
+                                           strings(f.find("labels")));
+        if (const Json* b = f.find("buckets")) fam->setBuckets(doubles(b));
+        families[name] = fam;
+      }
+    }
+    if (const Json* ops = script.find("ops")) {
+      for (auto& o : ops->array()) {
+        auto it = families.find(need(o, "family").str());
+        if (it == families.end())
+          throw std::runtime_error("op on an undeclared family");
+        std::string op = need(o, "op").str();
+        auto labels = strings(o.find("labels"));
+        const Json* value = o.find("value");
+        double v = value ? value->asDouble() : 0;
+        if (op == "inc") it->second->inc(labels, v);
+        else if (op == "set") it->second->set(labels, v);
+        else if (op == "observe") it->second->observe(labels, v);
+        else if (op == "setBuckets")
+          it->second->setBuckets(doubles(o.find("bounds")));
+        else throw std::runtime_error("unknown op: " + op);
+      }
+    }
+    return dupString(registry.expose());
+  } catch (const std::exception& e) {
+    if (errOut) *errOut = dupString(e.what());
+    return nullptr;
+  }
+}
+
+// What POST /v3/metric puts after "name|" for one JSON value.
+char* cp_metric_value_string(const char* jsonText, char** errOut) {
+  try {
+    return dupString(metricValueString(parseJson5(jsonText)));
+  } catch (const std::exception& e) {
+    if (errOut) *errOut = dupString(e.what());
+    return nullptr;
+  }
 }
 
 }  // extern "C"

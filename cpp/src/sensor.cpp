@@ -291,19 +291,9 @@ bool extract(const std::string& body, const RecordSpec& rec, double* out,
   return true;
 }
 
-std::string formatValue(double v) {
-  char buf[40];
-  // whole numbers read better as digits than as "4e+01"
-  if (std::fabs(v) < 1e15 && v == std::floor(v)) {
-    snprintf(buf, sizeof(buf), "%.0f", v);
-    return buf;
-  }
-  for (int prec = 1; prec <= 17; prec++) {
-    snprintf(buf, sizeof(buf), "%.*g", prec, v);
-    if (strtod(buf, nullptr) == v) break;
-  }
-  return buf;
-}
+// the exposition's printer, so a sample reads the same on /metrics as in
+// the event that carried it
+std::string formatValue(double v) { return prom::formatValue(v); }
 
 bool CounterBaseline::feed(double value, double* delta) {
   if (!have_) {

@@ -1,6 +1,9 @@
 #include "cpilot/telemetry.hpp"
 
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
+#include <strings.h>
 #include <thread>
 
 #include "cpilot/decode.hpp"
@@ -14,7 +17,8 @@ namespace cpilot {
 
 bool newMetricConfigs(const Json& raw,
                       std::vector<std::shared_ptr<MetricConfig>>* out,
-                      std::string* err) {
+                      std::string* err, prom::Registry* registry) {
+  if (!registry) registry = &prom::Registry::global();
   out->clear();
   if (raw.isNull()) return true;
   if (!raw.isArray()) {
@@ -62,9 +66,20 @@ bool newMetricConfigs(const Json& raw,
       *err = "invalid metric type: " + cfg->type;
       return false;
     }
+    // what prometheus.Register refuses in the reference
+    if (!prom::validMetricName(fq)) {
+      *err = "MetricConfig configuration error: \"" + fq +
+             "\" is not a valid metric name";
+      return false;
+    }
+    if (prom::isInternalName(fq)) {
+      *err = "MetricConfig configuration error: \"" + fq +
+             "\" is the name of an internal metric";
+      return false;
+    }
     // unregister-then-register so reloads survive
     // (telemetry/metrics_config.go:83-85)
-    cfg->collector = prom::Registry::global().registerFamily(
+    cfg->collector = registry->registerFamily(
         fq, cfg->help, cfg->metricType, {}, /*keepExisting=*/false);
     out->push_back(cfg);
   }
@@ -86,8 +101,10 @@ void Metric::onEvent(const Event& event) {
       LOG_ERROR("metric: invalid metric format: %s", event.source.c_str());
       return;
     }
+    // strings.Split(source, "|")[1]: up to a second "|"
     std::string key = event.source.substr(0, pipe);
     std::string val = event.source.substr(pipe + 1);
+    val = val.substr(0, val.find('|'));
     if (key == cfg_->fullName) record(val);
     return;
   }
@@ -96,27 +113,110 @@ void Metric::onEvent(const Event& event) {
   }
 }
 
+namespace {
+
+// length of the white-space character (unicode.IsSpace) at s[i], or 0
+size_t spaceAt(const std::string& s, size_t i) {
+  unsigned char c = (unsigned char)s[i];
+  if (c == ' ' || (c >= '\t' && c <= '\r')) return 1;
+  auto at = [&](size_t k) {
+    return i + k < s.size() ? (unsigned char)s[i + k] : 0;
+  };
+  if (c == 0xC2 && (at(1) == 0x85 || at(1) == 0xA0)) return 2;
+  if (c == 0xE1 && at(1) == 0x9A && at(2) == 0x80) return 3;  // U+1680
+  if (c == 0xE2 && at(1) == 0x80) {
+    unsigned char d = at(2);  // U+2000-200A, U+2028, U+2029, U+202F
+    if ((d >= 0x80 && d <= 0x8A) || d == 0xA8 || d == 0xA9 || d == 0xAF)
+      return 3;
+  }
+  if (c == 0xE2 && at(1) == 0x81 && at(2) == 0x9F) return 3;  // U+205F
+  if (c == 0xE3 && at(1) == 0x80 && at(2) == 0x80) return 3;  // U+3000
+  return 0;
+}
+
+std::string trimSpace(const std::string& s) {
+  size_t a = 0, b = s.size();
+  while (a < b) {
+    size_t n = spaceAt(s, a);
+    if (!n || a + n > b) break;
+    a += n;
+  }
+  while (b > a) {
+    // a white-space character ends at b: try its three possible lengths
+    size_t n = 0;
+    for (size_t len = 1; len <= 3 && len <= b - a; len++)
+      if (spaceAt(s, b - len) == len) n = len;
+    if (!n) break;
+    b -= n;
+  }
+  return s.substr(a, b - a);
+}
+
+}  // namespace
+
+bool parseMetricValue(const std::string& text, double* out) {
+  std::string v = trimSpace(text);
+  size_t i = 0;
+  bool neg = false, sign = false;
+  if (i < v.size() && (v[i] == '+' || v[i] == '-')) {
+    neg = v[i] == '-';
+    sign = true;
+    i++;
+  }
+  const char* rest = v.c_str() + i;
+  if (v.size() - i == strlen(rest)) {  // no embedded NUL
+    if (!strcasecmp(rest, "inf") || !strcasecmp(rest, "infinity")) {
+      *out = neg ? -INFINITY : INFINITY;
+      return true;
+    }
+    if (!sign && !strcasecmp(rest, "nan")) {
+      *out = std::nan("");
+      return true;
+    }
+  }
+  auto digits = [&] {
+    size_t n = 0;
+    while (i < v.size() && v[i] >= '0' && v[i] <= '9') i++, n++;
+    return n;
+  };
+  size_t mantissa = digits();
+  if (i < v.size() && v[i] == '.') {
+    i++;
+    mantissa += digits();
+  }
+  if (!mantissa) return false;
+  if (i < v.size() && (v[i] == 'e' || v[i] == 'E')) {
+    i++;
+    if (i < v.size() && (v[i] == '+' || v[i] == '-')) i++;
+    if (!digits()) return false;
+  }
+  if (i != v.size()) return false;
+  // the text is plain decimal now, which strtod rounds as Go does
+  double val = strtod(v.c_str(), nullptr);
+  if (std::isinf(val)) return false;  // Go: value out of range
+  *out = val;
+  return true;
+}
+
 void Metric::record(const std::string& value) {
   // TrimSpace + ParseFloat (telemetry/metrics.go:61-80)
-  std::string v = value;
-  size_t a = 0, b = v.size();
-  while (a < b && isspace((unsigned char)v[a])) a++;
-  while (b > a && isspace((unsigned char)v[b - 1])) b--;
-  v = v.substr(a, b - a);
-  char* end = nullptr;
-  double val = strtod(v.c_str(), &end);
-  if (v.empty() || !end || *end != '\0') {
-    LOG_ERROR("metric produced non-numeric value: %s", value.c_str());
-    return;
+  double val = 0;
+  bool ok = parseMetricValue(value, &val);
+  if (ok) {
+    switch (cfg_->metricType) {
+      case prom::MetricType::Counter:
+        ok = cfg_->collector->inc({}, val);
+        break;
+      case prom::MetricType::Gauge: cfg_->collector->set({}, val); break;
+      case prom::MetricType::Histogram:
+      case prom::MetricType::Summary:
+        ok = cfg_->collector->observe({}, val);
+        break;
+    }
   }
-  switch (cfg_->metricType) {
-    case prom::MetricType::Counter: cfg_->collector->inc({}, val); break;
-    case prom::MetricType::Gauge: cfg_->collector->set({}, val); break;
-    case prom::MetricType::Histogram:
-    case prom::MetricType::Summary:
-      cfg_->collector->observe({}, val);
-      break;
-  }
+  // a value its collector refuses (a negative or NaN counter increment, a
+  // NaN observation) is logged like one that is no number
+  if (!ok) LOG_ERROR("metric produced non-numeric value: %s", value.c_str());
 }
 
 // ---------------- telemetry config ----------------

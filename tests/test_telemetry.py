@@ -5,8 +5,11 @@ metric events via the control plane.
 
 import json
 import socket
+import subprocess
 import time
 import urllib.request
+
+from containerpilot_amd import BINARY, prommodel
 
 
 def wait_until(predicate, timeout=15.0, interval=0.1):
@@ -188,5 +191,99 @@ def test_histogram_and_summary_metrics(daemon_factory, mock_consul):
     assert "app_rq_latency_sum" in body
     assert 'app_rq_sizes{quantile="0.5"}' in body
     assert "app_rq_sizes_count 4" in body
+    d.terminate()
+    assert d.wait(timeout=30) == 0
+
+
+def test_posted_values_reach_metrics_exactly_and_survive_a_reload(
+        daemon_factory, mock_consul):
+    """Values that need 11, 17 and 16 digits, posted through /v3/metric
+    and through -putmetric, are scraped back bit for bit; the whole
+    exposition parses strictly before and after a reload, the dispatch
+    histogram stays consistent across it, and user metrics start over
+    (they unregister then register)."""
+    port = free_port()
+    names = ["t", "f", "big", "cli_t", "cli_f", "cli_big"]
+    d = daemon_factory({
+        "consul": mock_consul.address,
+        "stopTimeout": 1,
+        "jobs": [{"name": "main-app", "exec": "sleep 60"}],
+        "telemetry": {
+            "port": port,
+            "interfaces": ["static:127.0.0.1"],
+            "metrics": [
+                {"namespace": "app", "subsystem": "e2e", "name": n,
+                 "help": "first line\nsecond \\ line",
+                 "type": "counter" if n.endswith("big") else "gauge"}
+                for n in names],
+        },
+    }).start()
+    d.wait_for_socket()
+    url = "http://127.0.0.1:%d/metrics" % port
+    assert wait_until(lambda: _up(url))
+
+    def samples():
+        families = prommodel.parse_exposition(http_get(url)[1])
+        return families, {s.name: s for f in families for s in f.samples
+                          if not s.labels}
+
+    status, _ = d.control(
+        "POST", "/v3/metric",
+        '{"app_e2e_t": 1700000000.5, "app_e2e_f": 0.30000000000000004, '
+        '"app_e2e_big": 9007199254740992}')
+    assert status == 200
+    out = subprocess.run(
+        [BINARY, "-config", d.config_path,
+         "-putmetric", "app_e2e_cli_t=1700000000.5",
+         "-putmetric", "app_e2e_cli_f=0.30000000000000004",
+         "-putmetric", "app_e2e_cli_big=9007199254740992"],
+        capture_output=True, text=True, timeout=10)
+    assert out.returncode == 0, out.stderr
+    assert wait_until(lambda: samples()[1]["app_e2e_cli_big"].value != 0)
+    families, got = samples()
+    want = {"t": "1700000000.5", "f": "0.30000000000000004",
+            "big": "9007199254740992"}
+    for prefix in ("", "cli_"):
+        for n, text in want.items():
+            s = got["app_e2e_" + prefix + n]
+            assert s.value == float(text) and s.text == text, s
+    # the names a user metric may not take are the families the daemon has
+    own = {f.name for f in families if f.name.startswith("containerpilot_")}
+    assert own and own <= set(prommodel.INTERNAL_FAMILIES), own
+    fam = [f for f in families if f.name == "app_e2e_t"][0]
+    assert fam.help == "first line\nsecond \\ line"
+    dispatch = [f for f in families
+                if f.name == "containerpilot_event_dispatch_seconds"][0]
+    assert prommodel.histogram_violations(dispatch) == []
+    count_before = got["containerpilot_event_dispatch_seconds_count"].value
+    assert count_before > 0
+    buckets_before = {s.label("le"): s.value for s in dispatch.samples
+                      if s.name.endswith("_bucket")}
+
+    status, _ = d.control("POST", "/v3/reload")
+    assert status == 200
+
+    def reloaded():
+        try:
+            return samples()[1]["app_e2e_big"].value == 0
+        except OSError:
+            return False  # the listener is between two generations
+    assert wait_until(reloaded)
+    d.wait_for_socket()
+    families, got = samples()
+    for n in names:
+        assert got["app_e2e_" + n].value == 0, n
+    dispatch = [f for f in families
+                if f.name == "containerpilot_event_dispatch_seconds"][0]
+    assert dispatch.type == "histogram"
+    assert prommodel.histogram_violations(dispatch) == []
+    # an internal collector lives on across generations
+    assert got["containerpilot_event_dispatch_seconds_count"].value \
+        >= count_before
+    buckets = {s.label("le"): s.value for s in dispatch.samples
+               if s.name.endswith("_bucket")}
+    assert set(buckets) == set(buckets_before)
+    for le, before in buckets_before.items():
+        assert buckets[le] >= before, (le, before, buckets[le])
     d.terminate()
     assert d.wait(timeout=30) == 0
