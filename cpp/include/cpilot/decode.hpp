@@ -18,6 +18,10 @@ namespace decode {
 bool checkKeys(const Json& obj, const std::set<std::string>& allowed,
                std::string* err);
 
+// The value of `key` in `obj`, nullptr when the key is absent or null: an
+// option set to null counts as not given.
+const Json* given(const Json& obj, const char* key);
+
 // weak int: accepts Int, Double (truncates), numeric String, Bool(0/1)
 bool toInt(const Json& v, int* out);
 // weak string: String, or number rendered as text

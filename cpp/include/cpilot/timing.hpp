@@ -26,6 +26,11 @@ Duration parseDuration(const Json& v);
 // GetTimeout: empty string -> 0, otherwise parseDuration.
 Duration getTimeout(const std::string& s);
 
+// health.interval's rule, shared by every interval and timeout that must
+// be positive: an int is seconds, a string is a duration that starts with a
+// digit; at least a millisecond. False for anything else.
+bool parsePositiveDuration(const Json& v, Duration* out);
+
 // Render a duration the way Go's Duration.String() would for whole seconds
 // ("5s"); used for Consul TTL strings.
 std::string secondsString(int seconds);

@@ -22,6 +22,11 @@ bool checkKeys(const Json& obj, const std::set<std::string>& allowed,
   return true;
 }
 
+const Json* given(const Json& obj, const char* key) {
+  const Json* v = obj.find(key);
+  return v && !v->isNull() ? v : nullptr;
+}
+
 bool toInt(const Json& v, int* out) {
   if (v.isInt()) {
     *out = (int)v.asInt();

@@ -213,24 +213,12 @@ bool validateHealthCheck(const Json& raw, std::shared_ptr<JobConfig>& cfg,
   // baseline's 100ms are expressible)
   Duration heartbeat{0};
   int ttl = 0;
-  if (const Json* v = health->find("interval")) {
-    if (v->isString() && !v->str().empty() &&
-        !isdigit((unsigned char)v->str()[0]) ) {
-      *err = "job[" + cfg->name + "].health.interval must be > 0";
-      return false;
-    }
-    try {
-      heartbeat = parseDuration(*v);
-    } catch (const std::exception&) {
-      *err = "job[" + cfg->name + "].health.interval must be > 0";
-      return false;
-    }
-  }
-  if (const Json* v = health->find("ttl")) decode::toInt(*v, &ttl);
-  if (heartbeat < std::chrono::milliseconds(1)) {
+  const Json* interval = health->find("interval");
+  if (!interval || !parsePositiveDuration(*interval, &heartbeat)) {
     *err = "job[" + cfg->name + "].health.interval must be > 0";
     return false;
   }
+  if (const Json* v = health->find("ttl")) decode::toInt(*v, &ttl);
   if (ttl < 1) {
     *err = "job[" + cfg->name + "].health.ttl must be > 0";
     return false;
@@ -252,26 +240,26 @@ bool validateHealthCheck(const Json& raw, std::shared_ptr<JobConfig>& cfg,
     }
   }
 
-  const Json* checkExec = health->find("exec");
-  const Json* checkHttp = health->find("http");
-  const Json* checkTcp = health->find("tcp");
-  auto given = [](const Json* v) { return v && !v->isNull(); };
-  if (given(checkExec) + given(checkHttp) + given(checkTcp) > 1) {
+  const Json* checkExec = decode::given(*health, "exec");
+  const Json* checkHttp = decode::given(*health, "http");
+  const Json* checkTcp = decode::given(*health, "tcp");
+  if ((checkExec != nullptr) + (checkHttp != nullptr) + (checkTcp != nullptr) >
+      1) {
     *err = "job[" + cfg->name +
            "].health can have only one of 'exec', 'http', or 'tcp'";
     return false;
   }
-  if (given(checkHttp) || given(checkTcp)) {
+  if (checkHttp || checkTcp) {
     // native probes: run on the reactor, nothing is spawned, so there is
     // no child output to wrap or pass through
-    if (given(health->find("logging"))) {
+    if (decode::given(*health, "logging")) {
       *err = "job[" + cfg->name + "].health.logging only applies to "
              "'exec' checks; 'http' and 'tcp' checks have no output";
       return false;
     }
     health::ProbeSpec spec;
     std::string probeErr;
-    if (given(checkTcp)) {
+    if (checkTcp) {
       if (!checkTcp->isString()) {
         *err = "job[" + cfg->name + "].health.tcp must be a \"HOST:PORT\" "
                "string";
@@ -297,7 +285,7 @@ bool validateHealthCheck(const Json& raw, std::shared_ptr<JobConfig>& cfg,
         std::move(spec), "check." + cfg->name);
     return true;
   }
-  if (checkExec && !checkExec->isNull()) {
+  if (checkExec) {
     std::string checkName = "check." + cfg->name;
     bool raw_ = false;
     std::string boolErr;
@@ -453,17 +441,13 @@ bool validateSignal(const Json& raw, std::shared_ptr<JobConfig>& cfg,
                     std::string* err) {
   const Json* sig = raw.find("signal");
   if (!sig || sig->isNull()) return true;
-  auto given = [&](const char* key) {
-    const Json* v = raw.find(key);
-    return v && !v->isNull();
-  };
-  if (given("exec")) {
+  if (decode::given(raw, "exec")) {
     *err = "job[" + cfg->name + "].signal cannot be combined with 'exec'";
     return false;
   }
   // no child, no output and nothing to register
   for (const char* key : {"port", "health", "timeout", "logging"}) {
-    if (given(key)) {
+    if (decode::given(raw, key)) {
       *err = "job[" + cfg->name + "].signal cannot be combined with '" + key +
              "': a signal job starts no process";
       return false;

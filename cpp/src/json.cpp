@@ -6,6 +6,8 @@
 #include <cstring>
 #include <sstream>
 
+#include "cpilot/gotext.hpp"
+
 namespace cpilot {
 
 namespace {
@@ -247,7 +249,7 @@ class Parser {
               pos_ = save;
             }
           }
-          appendUtf8(out, cp);
+          gotext::appendUtf8(out, cp);
           break;
         }
         default:
@@ -260,32 +262,11 @@ class Parser {
   unsigned parseHex(int n) {
     unsigned v = 0;
     for (int i = 0; i < n; i++) {
-      char c = get();
-      v <<= 4;
-      if (c >= '0' && c <= '9') v += c - '0';
-      else if (c >= 'a' && c <= 'f') v += c - 'a' + 10;
-      else if (c >= 'A' && c <= 'F') v += c - 'A' + 10;
-      else { pos_--; fail("invalid hex digit"); }
+      int d = gotext::hexVal(get());
+      if (d < 0) { pos_--; fail("invalid hex digit"); }
+      v = (v << 4) + (unsigned)d;
     }
     return v;
-  }
-
-  static void appendUtf8(std::string& out, unsigned cp) {
-    if (cp < 0x80) {
-      out += (char)cp;
-    } else if (cp < 0x800) {
-      out += (char)(0xC0 | (cp >> 6));
-      out += (char)(0x80 | (cp & 0x3F));
-    } else if (cp < 0x10000) {
-      out += (char)(0xE0 | (cp >> 12));
-      out += (char)(0x80 | ((cp >> 6) & 0x3F));
-      out += (char)(0x80 | (cp & 0x3F));
-    } else {
-      out += (char)(0xF0 | (cp >> 18));
-      out += (char)(0x80 | ((cp >> 12) & 0x3F));
-      out += (char)(0x80 | ((cp >> 6) & 0x3F));
-      out += (char)(0x80 | (cp & 0x3F));
-    }
   }
 
   Json parseNumber() {
@@ -304,8 +285,7 @@ class Parser {
       int64_t v = 0;
       bool any = false;
       while (!eof() && isxdigit((unsigned char)peek())) {
-        char c = get();
-        v = v * 16 + (c <= '9' ? c - '0' : (tolower(c) - 'a' + 10));
+        v = v * 16 + gotext::hexVal(get());
         any = true;
       }
       if (!any) fail("invalid hex number");

@@ -33,6 +33,12 @@ bool isSpace(char c) {
          c == '\r';
 }
 
+// narrows [*a, *b) of s past the white space at either end
+void trimRange(const std::string& s, size_t* a, size_t* b) {
+  while (*a < *b && isSpace(s[*a])) (*a)++;
+  while (*b > *a && isSpace(s[*b - 1])) (*b)--;
+}
+
 std::string notANumber(const std::string& token) {
   // a NUL would end the reason early in every C string it passes through
   std::string shown;
@@ -63,8 +69,8 @@ bool findLine(const std::string& body, int64_t want, const std::string& prefix,
         return true;
       }
     } else {
-      size_t a = pos;
-      while (a < stop && isSpace(body[a])) a++;
+      size_t a = pos, b = stop;
+      trimRange(body, &a, &b);
       if (stop - a >= prefix.size() &&
           body.compare(a, prefix.size(), prefix) == 0) {
         *begin = pos;
@@ -192,21 +198,6 @@ bool extractJson(const std::string& body, const RecordSpec& rec, double* out,
   return false;
 }
 
-// health.interval's rule: an int is seconds, a string is a duration that
-// starts with a digit; at least a millisecond
-bool parsePositiveDuration(const Json& v, Duration* out) {
-  if (v.isString() &&
-      (v.str().empty() || !isdigit((unsigned char)v.str()[0])))
-    return false;
-  if (!v.isString() && !v.isNumber()) return false;
-  try {
-    *out = parseDuration(v);
-  } catch (const std::exception&) {
-    return false;
-  }
-  return *out >= std::chrono::milliseconds(1);
-}
-
 std::string numericTarget(const health::ProbeSpec& spec) {
   char buf[INET6_ADDRSTRLEN] = {0};
   int port = 0;
@@ -228,8 +219,7 @@ std::string numericTarget(const health::ProbeSpec& spec) {
 
 bool parseNumber(const std::string& token, double* out) {
   size_t a = 0, b = token.size();
-  while (a < b && isSpace(token[a])) a++;
-  while (b > a && isSpace(token[b - 1])) b--;
+  trimRange(token, &a, &b);
   if (a == b) return false;
   std::string v = token.substr(a, b - a);
   char* end = nullptr;
@@ -248,8 +238,7 @@ bool extract(const std::string& body, const RecordSpec& rec, double* out,
     case RecordSpec::Selector::Whole: {
       if (!parseNumber(body, &value)) {
         size_t a = 0, b = body.size();
-        while (a < b && isSpace(body[a])) a++;
-        while (b > a && isSpace(body[b - 1])) b--;
+        trimRange(body, &a, &b);
         *reason = notANumber(body.substr(a, b - a));
         return false;
       }
@@ -371,14 +360,10 @@ bool parseRecord(const Json& raw, RecordSpec* out, std::string* errKey,
   }
   out->metric = metric->str();
 
-  auto given = [&](const char* key) {
-    const Json* v = raw.find(key);
-    return v && !v->isNull() ? v : nullptr;
-  };
-  const Json* line = given("line");
-  const Json* lineNumber = given("lineNumber");
-  const Json* field = given("field");
-  const Json* json = given("json");
+  const Json* line = decode::given(raw, "line");
+  const Json* lineNumber = decode::given(raw, "lineNumber");
+  const Json* field = decode::given(raw, "field");
+  const Json* json = decode::given(raw, "json");
   if (json && (line || lineNumber || field)) {
     *errKey = ".json";
     *err = "cannot be combined with 'line', 'lineNumber' or 'field'";
@@ -436,7 +421,7 @@ bool parseRecord(const Json& raw, RecordSpec* out, std::string* errKey,
     }
     out->field = field->asInt();
   }
-  if (const Json* scale = given("scale")) {
+  if (const Json* scale = decode::given(raw, "scale")) {
     if (!scale->isNumber() || !std::isfinite(scale->asDouble())) {
       *errKey = ".scale";
       *err = "must be a finite number";
@@ -489,12 +474,8 @@ bool newSensorSpecs(const Json& raw,
       return false;
     }
 
-    auto given = [&](const char* key) {
-      const Json* v = s.find(key);
-      return v && !v->isNull() ? v : nullptr;
-    };
-    const Json* file = given("file");
-    const Json* http = given("http");
+    const Json* file = decode::given(s, "file");
+    const Json* http = decode::given(s, "http");
     if ((file != nullptr) == (http != nullptr)) {
       *err = at + " needs exactly one of 'file' and 'http'";
       return false;
@@ -524,13 +505,13 @@ bool newSensorSpecs(const Json& raw,
       spec->httpTarget = numericTarget(spec->http);
     }
 
-    const Json* interval = given("interval");
+    const Json* interval = decode::given(s, "interval");
     if (!interval || !parsePositiveDuration(*interval, &spec->interval)) {
       *err = at + ".interval must be > 0";
       return false;
     }
     spec->timeout = spec->interval;
-    if (const Json* timeout = given("timeout")) {
+    if (const Json* timeout = decode::given(s, "timeout")) {
       if (!parsePositiveDuration(*timeout, &spec->timeout)) {
         *err = at + ".timeout must be > 0";
         return false;
@@ -538,7 +519,7 @@ bool newSensorSpecs(const Json& raw,
     }
     spec->http.timeout = spec->timeout;
 
-    const Json* record = given("record");
+    const Json* record = decode::given(s, "record");
     if (!record || !record->isArray() || record->array().empty()) {
       *err = at + ".record must be a non-empty array";
       return false;

@@ -1,12 +1,10 @@
 #include "cpilot/telemetry.hpp"
 
-#include <cmath>
 #include <cstdlib>
-#include <cstring>
-#include <strings.h>
 #include <thread>
 
 #include "cpilot/decode.hpp"
+#include "cpilot/gotext.hpp"
 #include "cpilot/ips.hpp"
 #include "cpilot/log.hpp"
 #include "cpilot/version.hpp"
@@ -113,89 +111,8 @@ void Metric::onEvent(const Event& event) {
   }
 }
 
-namespace {
-
-// length of the white-space character (unicode.IsSpace) at s[i], or 0
-size_t spaceAt(const std::string& s, size_t i) {
-  unsigned char c = (unsigned char)s[i];
-  if (c == ' ' || (c >= '\t' && c <= '\r')) return 1;
-  auto at = [&](size_t k) {
-    return i + k < s.size() ? (unsigned char)s[i + k] : 0;
-  };
-  if (c == 0xC2 && (at(1) == 0x85 || at(1) == 0xA0)) return 2;
-  if (c == 0xE1 && at(1) == 0x9A && at(2) == 0x80) return 3;  // U+1680
-  if (c == 0xE2 && at(1) == 0x80) {
-    unsigned char d = at(2);  // U+2000-200A, U+2028, U+2029, U+202F
-    if ((d >= 0x80 && d <= 0x8A) || d == 0xA8 || d == 0xA9 || d == 0xAF)
-      return 3;
-  }
-  if (c == 0xE2 && at(1) == 0x81 && at(2) == 0x9F) return 3;  // U+205F
-  if (c == 0xE3 && at(1) == 0x80 && at(2) == 0x80) return 3;  // U+3000
-  return 0;
-}
-
-std::string trimSpace(const std::string& s) {
-  size_t a = 0, b = s.size();
-  while (a < b) {
-    size_t n = spaceAt(s, a);
-    if (!n || a + n > b) break;
-    a += n;
-  }
-  while (b > a) {
-    // a white-space character ends at b: try its three possible lengths
-    size_t n = 0;
-    for (size_t len = 1; len <= 3 && len <= b - a; len++)
-      if (spaceAt(s, b - len) == len) n = len;
-    if (!n) break;
-    b -= n;
-  }
-  return s.substr(a, b - a);
-}
-
-}  // namespace
-
 bool parseMetricValue(const std::string& text, double* out) {
-  std::string v = trimSpace(text);
-  size_t i = 0;
-  bool neg = false, sign = false;
-  if (i < v.size() && (v[i] == '+' || v[i] == '-')) {
-    neg = v[i] == '-';
-    sign = true;
-    i++;
-  }
-  const char* rest = v.c_str() + i;
-  if (v.size() - i == strlen(rest)) {  // no embedded NUL
-    if (!strcasecmp(rest, "inf") || !strcasecmp(rest, "infinity")) {
-      *out = neg ? -INFINITY : INFINITY;
-      return true;
-    }
-    if (!sign && !strcasecmp(rest, "nan")) {
-      *out = std::nan("");
-      return true;
-    }
-  }
-  auto digits = [&] {
-    size_t n = 0;
-    while (i < v.size() && v[i] >= '0' && v[i] <= '9') i++, n++;
-    return n;
-  };
-  size_t mantissa = digits();
-  if (i < v.size() && v[i] == '.') {
-    i++;
-    mantissa += digits();
-  }
-  if (!mantissa) return false;
-  if (i < v.size() && (v[i] == 'e' || v[i] == 'E')) {
-    i++;
-    if (i < v.size() && (v[i] == '+' || v[i] == '-')) i++;
-    if (!digits()) return false;
-  }
-  if (i != v.size()) return false;
-  // the text is plain decimal now, which strtod rounds as Go does
-  double val = strtod(v.c_str(), nullptr);
-  if (std::isinf(val)) return false;  // Go: value out of range
-  *out = val;
-  return true;
+  return gotext::parseFloat(gotext::trimSpace(text), out);
 }
 
 void Metric::record(const std::string& value) {

@@ -4,6 +4,8 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "cpilot/gotext.hpp"
+
 namespace cpilot {
 
 namespace {
@@ -12,24 +14,6 @@ constexpr uint64_t kTwo63 = (uint64_t)1 << 63;
 
 [[noreturn]] void invalidDuration(const std::string& s) {
   throw std::runtime_error("time: invalid duration " + s);
-}
-
-// [+-]?[0-9]+ that fits an int64: what strconv.Atoi accepts
-bool strictAtoi(const std::string& s, int64_t* out) {
-  size_t i = 0;
-  bool neg = false;
-  if (i < s.size() && (s[i] == '+' || s[i] == '-')) neg = s[i++] == '-';
-  if (i == s.size()) return false;
-  uint64_t v = 0;
-  for (; i < s.size(); i++) {
-    if (s[i] < '0' || s[i] > '9') return false;
-    uint64_t d = (uint64_t)(s[i] - '0');
-    if (v > (kTwo63 - d) / 10) return false;
-    v = v * 10 + d;
-  }
-  if (!neg && v == kTwo63) return false;
-  *out = neg ? (int64_t)(0 - v) : (int64_t)v;
-  return true;
 }
 
 Duration secondsToDuration(int64_t sec) {
@@ -133,7 +117,8 @@ Duration parseDuration(const Json& v) {
     // a string strconv.Atoi accepts = seconds, parsed as "<n>s"
     // (duration.go:53-55), so it overflows like any other duration
     int64_t sec = 0;
-    if (strictAtoi(s, &sec)) return parseGoDuration(std::to_string(sec) + "s");
+    if (gotext::atoi(s, &sec))
+      return parseGoDuration(std::to_string(sec) + "s");
     return parseGoDuration(s);
   }
   throw std::runtime_error("unexpected duration type");
@@ -142,6 +127,19 @@ Duration parseDuration(const Json& v) {
 Duration getTimeout(const std::string& s) {
   if (s.empty()) return Duration(0);
   return parseDuration(Json(s));
+}
+
+bool parsePositiveDuration(const Json& v, Duration* out) {
+  if (v.isString() &&
+      (v.str().empty() || !isdigit((unsigned char)v.str()[0])))
+    return false;
+  if (!v.isString() && !v.isNumber()) return false;
+  try {
+    *out = parseDuration(v);
+  } catch (const std::exception&) {
+    return false;
+  }
+  return *out >= std::chrono::milliseconds(1);
 }
 
 std::string secondsString(int seconds) {

@@ -1,7 +1,8 @@
 // Tests for the Prometheus client (cpilot/metrics.hpp) and the value rule
-// of user metrics (parseMetricValue in cpilot/telemetry.hpp): the float
-// printer, name rules, nearest-rank quantiles, bucket state across
-// setBuckets, the refusals, and, given the path of
+// of user metrics (parseMetricValue in cpilot/telemetry.hpp, which trims
+// and then applies gotext::parseFloat): the float printer, name rules,
+// nearest-rank quantiles, bucket state across setBuckets, the refusals,
+// and, given the path of
 // tests/golden/metrics_cases.json, a replay of every row of that table
 // through the same hooks the Python harness calls.
 // Run via `bin/cpilot_metricstests [table.json]`; exits non-zero if any
@@ -113,44 +114,23 @@ void expectRefused(const char* text, int line) {
 #define VALUE(text, want) expectValue(text, want, __LINE__)
 #define REFUSED(text) expectRefused(text, __LINE__)
 
+// TrimSpace, then ParseFloat: the float rules have their rows in
+// unittests.cpp's testGoText; these show that the wrapper trims Go's white
+// space, and nothing else, before it applies them
 void testParseMetricValue() {
   VALUE("1", 1);
   VALUE(" \t7.5\r\n", 7.5);
   VALUE("\xc2\xa0\xe3\x80\x80" "7.5" "\xc2\x85\xe2\x80\x83", 7.5);
-  VALUE(".5", 0.5);
-  VALUE("5.", 5);
-  VALUE("+5", 5);
-  VALUE("-0", -0.0);
-  VALUE("1E1", 10);
-  VALUE("1e-999", 0);
-  VALUE("-1e-999", -0.0);
-  VALUE("1.7976931348623157e308", std::numeric_limits<double>::max());
-  VALUE("inf", kInf);
-  VALUE("+Infinity", kInf);
-  VALUE("-INF", -kInf);
-  VALUE("NaN", kNaN);
+  VALUE(" -INF\n", -kInf);
+  VALUE("\tNaN ", kNaN);
   REFUSED("");
   REFUSED(" ");
-  REFUSED("0x1p3");
-  REFUSED("0x10");
-  REFUSED("1_000");
-  REFUSED("nan(x)");
-  REFUSED("+nan");
-  REFUSED("-nan");
-  REFUSED("--1");
-  REFUSED(".");
-  REFUSED("1e");
-  REFUSED("1e+");
-  REFUSED("e5");
-  REFUSED("1e999");
-  REFUSED("-1e999");
   REFUSED("1 2");
+  REFUSED(" 1e999 ");
   REFUSED("\xe2\x80\x8b" "7");  // U+200B is no white space
   REFUSED("\x85" "7");          // nor is a lone continuation byte
-  REFUSED("infinit");
   double got = 0;
-  CHECK(!parseMetricValue(std::string("1\0" "2", 3), &got));
-  CHECK(!parseMetricValue(std::string("inf\0", 4), &got));
+  CHECK(!parseMetricValue(std::string(" 1\0" "2 ", 5), &got));
 }
 
 void testSummary() {

@@ -10,7 +10,9 @@
 
 #include <atomic>
 #include <cassert>
+#include <cmath>
 #include <cstdio>
+#include <limits>
 #include <thread>
 #include <vector>
 #include <cstdlib>
@@ -29,6 +31,7 @@
 #include "cpilot/jobs.hpp"
 #include "cpilot/decode.hpp"
 #include "cpilot/events.hpp"
+#include "cpilot/gotext.hpp"
 #include "cpilot/http.hpp"
 #include "cpilot/ips.hpp"
 #include "cpilot/json.hpp"
@@ -38,8 +41,10 @@
 using namespace cpilot;
 
 static int failures = 0;
+static std::atomic<int> checks{0};  // CHECKs run on helper threads too
 #define CHECK(cond)                                                       \
   do {                                                                    \
+    checks++;                                                             \
     if (!(cond)) {                                                        \
       fprintf(stderr, "FAIL %s:%d: %s\n", __FILE__, __LINE__, #cond);     \
       failures++;                                                         \
@@ -49,6 +54,7 @@ static int failures = 0;
   do {                                                                    \
     auto va = (a);                                                        \
     auto vb = (b);                                                        \
+    checks++;                                                             \
     if (!(va == vb)) {                                                    \
       fprintf(stderr, "FAIL %s:%d: %s != %s\n", __FILE__, __LINE__, #a,   \
               #b);                                                        \
@@ -1324,6 +1330,256 @@ static void testUnixPathTooLong() {
   CHECK_EQ(rmdir(dir.c_str()), 0);  // so the directory is still empty
 }
 
+// The shared Go text rules (cpilot/gotext.hpp) on their own: every feature
+// that reads text through them is tested elsewhere, through the feature.
+// Returns the number of checks made.
+static int testGoText() {
+  using namespace gotext;
+  const int before = checks;
+  auto bytes = [](const char* s, size_t n) { return std::string(s, n); };
+  auto enc = [](uint32_t cp) {
+    std::string out;
+    appendUtf8(out, cp);
+    return out;
+  };
+
+  // ---- UTF-8: the boundary code points of each length ----
+  struct Boundary {
+    uint32_t cp;
+    const char* utf8;
+    size_t len;
+  };
+  const Boundary boundaries[] = {
+      {0x7F, "\x7F", 1},         {0x80, "\xC2\x80", 2},
+      {0x7FF, "\xDF\xBF", 2},    {0x800, "\xE0\xA0\x80", 3},
+      {0xFFFF, "\xEF\xBF\xBF", 3}, {0x10000, "\xF0\x90\x80\x80", 4},
+      {0x10FFFF, "\xF4\x8F\xBF\xBF", 4},
+  };
+  std::string all;
+  for (auto& b : boundaries) {
+    std::string s(b.utf8, b.len);
+    CHECK_EQ(enc(b.cp), s);
+    uint32_t cp = 0;
+    CHECK_EQ(utf8SeqLen(s, 0, &cp), b.len);
+    CHECK_EQ(cp, b.cp);
+    CHECK_EQ(utf8SeqLen("x" + s + "x", 1), b.len);
+    CHECK_EQ(runeCount(s), (size_t)1);
+    all += s;
+  }
+  std::u32string cps;
+  CHECK(decodeUtf8(all, &cps));
+  CHECK_EQ(cps.size(), sizeof(boundaries) / sizeof(boundaries[0]));
+  CHECK(cps.size() == 7 && cps[0] == 0x7F && cps[3] == 0x800 &&
+        cps[6] == 0x10FFFF);
+  CHECK_EQ(runeCount(all), (size_t)7);
+  CHECK(decodeUtf8("", &cps));
+  CHECK(cps.empty());
+  CHECK_EQ(runeCount(""), (size_t)0);
+
+  // refused, and each byte of a refused sequence counts as one rune
+  const std::string refused[] = {
+      "\xED\xA0\x80",      // U+D800 encoded
+      "\xED\xBF\xBF",      // U+DFFF encoded
+      "\xF4\x90\x80\x80",  // U+110000
+      "\xC0\x80",          // overlong 2-byte forms
+      "\xC1\xBF",
+      "\xE0\x80\x80",      // overlong 3-byte forms
+      "\xE0\x9F\xBF",
+      "\xF0\x8F\xBF\xBF",  // overlong 4-byte form
+      "\xC2",              // truncated at the end of the string
+      "\xE2\x80",
+      "\xF0\x90\x80",
+      "\x80",              // a continuation byte alone
+      "\xF8\x88\x80\x80",  // no lead byte
+      "\xFF",
+      "\xC2\x41",          // lead byte without its continuation
+  };
+  for (auto& r : refused) {
+    CHECK_EQ(utf8SeqLen(r, 0), (size_t)0);
+    CHECK_EQ(utf8SeqLen("a" + r, 1), (size_t)0);
+    CHECK(!decodeUtf8(r, &cps));
+    CHECK(!decodeUtf8("ok" + r, &cps));
+    CHECK_EQ(runeCount(r), r.size());
+    CHECK_EQ(runeCount("\xE2\x82\xAC" + r), 1 + r.size());
+  }
+
+  // ---- white space ----
+  const uint32_t spaces[] = {0x09,   0x0A,   0x0B,   0x0C,   0x0D,  0x20,
+                             0x85,   0xA0,   0x1680, 0x2000, 0x2005, 0x200A,
+                             0x2028, 0x2029, 0x202F, 0x205F, 0x3000};
+  std::string everySpace;
+  for (uint32_t cp : spaces) {
+    CHECK(isSpace(cp));
+    std::string sp = enc(cp);
+    CHECK_EQ(trimSpace(sp + "x"), std::string("x"));
+    CHECK_EQ(trimSpace("x" + sp), std::string("x"));
+    CHECK_EQ(trimSpace(sp + "x" + sp), std::string("x"));
+    CHECK_EQ(trimSpace(sp + sp + "x y" + sp + sp), std::string("x y"));
+    everySpace += sp;
+  }
+  CHECK_EQ(trimSpace(everySpace), std::string(""));
+  CHECK_EQ(trimSpace(everySpace + "x" + everySpace), std::string("x"));
+  CHECK_EQ(trimSpace(""), std::string(""));
+  CHECK_EQ(trimSpace("x"), std::string("x"));
+  // the neighbours of the table's entries are no white space
+  const uint32_t nonSpaces[] = {0x08,   0x0E,   0x1F,   0x21,   0x84,  0x86,
+                                0x9F,   0xA1,   0x167F, 0x1681, 0x180E, 0x1FFF,
+                                0x200B, 0x200C, 0x2027, 0x202A, 0x202E, 0x2030,
+                                0x205E, 0x2060, 0x2FFF, 0x3001, 0xFEFF};
+  for (uint32_t cp : nonSpaces) {
+    CHECK(!isSpace(cp));
+    std::string kept = enc(cp) + "x" + enc(cp);
+    CHECK_EQ(trimSpace(kept), kept);
+    CHECK_EQ(trimSpace(" " + kept + "\t"), kept);
+    CHECK_EQ(trimSpace("\xE2\x80\x83" + kept + "\xC2\xA0"), kept);
+  }
+  // a malformed byte is no space: it stays and the trimming stops there
+  const std::string malformed[] = {
+      "\x85",      // the bytes of U+0085 and U+00A0 without their lead byte
+      "\xA0",
+      "\xC2",      // a lead byte whose continuation is missing
+      "\xE2\x80",  // two thirds of U+2000..U+200A
+      "\xC0\xA0",  // U+0020 in an overlong form
+  };
+  for (auto& m : malformed) {
+    CHECK_EQ(trimSpace(" x " + m), "x " + m);
+    CHECK_EQ(trimSpace(m + " x "), m + " x");
+    CHECK_EQ(trimSpace(" " + m + " "), m);
+    CHECK_EQ(trimSpace("\xC2\xA0 " + m), m);
+  }
+  CHECK_EQ(trimSpace(bytes(" \0 ", 3)), bytes("\0", 1));
+  CHECK_EQ(trimSpace(bytes(" a \0 b ", 7)), bytes("a \0 b", 5));
+
+  // ---- strconv.Atoi ----
+  auto atoiOf = [](const char* s, int64_t want) {
+    int64_t got = want ^ 1;
+    return atoi(s, &got) && got == want;
+  };
+  auto atoiRefuses = [](const std::string& s) {
+    int64_t got = 0;
+    return !atoi(s, &got);
+  };
+  CHECK(atoiOf("0", 0));
+  CHECK(atoiOf("-0", 0));
+  CHECK(atoiOf("+7", 7));
+  CHECK(atoiOf("007", 7));
+  CHECK(atoiOf("9223372036854775807", INT64_MAX));
+  CHECK(atoiOf("-9223372036854775808", INT64_MIN));
+  CHECK(atoiRefuses("9223372036854775808"));
+  CHECK(atoiRefuses("-9223372036854775809"));
+  CHECK(atoiRefuses("99999999999999999999"));
+  CHECK(atoiRefuses(""));
+  CHECK(atoiRefuses("+"));
+  CHECK(atoiRefuses("-"));
+  CHECK(atoiRefuses("1 "));
+  CHECK(atoiRefuses(" 1"));
+  CHECK(atoiRefuses("1_0"));
+  CHECK(atoiRefuses("0x1"));
+  CHECK(atoiRefuses("1.0"));
+  CHECK(atoiRefuses("--1"));
+  CHECK(atoiRefuses(bytes("1\0", 2)));
+
+  // ---- hex digits ----
+  CHECK_EQ(hexVal('0'), 0);
+  CHECK_EQ(hexVal('9'), 9);
+  CHECK_EQ(hexVal('a'), 10);
+  CHECK_EQ(hexVal('f'), 15);
+  CHECK_EQ(hexVal('A'), 10);
+  CHECK_EQ(hexVal('F'), 15);
+  for (char c : {'g', 'G', '/', ':', '@', '`', ' ', '\0', '\xE9'})
+    CHECK_EQ(hexVal(c), -1);
+
+  // ---- the decimal float grammar ----
+  for (const char* s : {"0", "12", ".5", "5.", "1.5", "1e5", "1E5", "1e+5",
+                        "1e-5", ".5e1", "5.e1", "007"})
+    CHECK(isDecimalFloat(s));
+  for (const char* s : {"", ".", "e5", ".e5", "1e", "1e+", "1e-", "+1", "-1",
+                        "1 ", " 1", "0x1", "1_0", "1.2.3", "1e5.0", "1f",
+                        "inf", "nan"})
+    CHECK(!isDecimalFloat(s));
+  CHECK(!isDecimalFloat(bytes("1\0", 2)));
+
+  // ---- strconv.ParseFloat ----
+  auto floatOf = [](const std::string& s, double want) {
+    double got = 0;
+    if (!parseFloat(s, &got)) return false;
+    if (std::isnan(want)) return std::isnan(got);
+    return got == want && std::signbit(got) == std::signbit(want);
+  };
+  auto floatRefuses = [](const std::string& s) {
+    double got = 0;
+    return !parseFloat(s, &got);
+  };
+  const double inf = std::numeric_limits<double>::infinity();
+  CHECK(floatOf("1", 1));
+  CHECK(floatOf("7.5", 7.5));
+  CHECK(floatOf(".5", 0.5));
+  CHECK(floatOf("5.", 5));
+  CHECK(floatOf("+5", 5));
+  CHECK(floatOf("-0", -0.0));
+  CHECK(floatOf("1E1", 10));
+  CHECK(floatOf("1e-999", 0));
+  CHECK(floatOf("-1e-999", -0.0));
+  CHECK(floatOf("1.7976931348623157e308", std::numeric_limits<double>::max()));
+  CHECK(floatOf("inf", inf));
+  CHECK(floatOf("+Infinity", inf));
+  CHECK(floatOf("-INF", -inf));
+  CHECK(floatOf("NaN", std::numeric_limits<double>::quiet_NaN()));
+  CHECK(floatRefuses(""));
+  CHECK(floatRefuses(" "));
+  CHECK(floatRefuses(" 1"));  // trimming is the caller's business
+  CHECK(floatRefuses("1 "));
+  CHECK(floatRefuses("0x1p3"));
+  CHECK(floatRefuses("0x10"));
+  CHECK(floatRefuses("1_000"));
+  CHECK(floatRefuses("nan(x)"));
+  CHECK(floatRefuses("+nan"));
+  CHECK(floatRefuses("-nan"));
+  CHECK(floatRefuses("--1"));
+  CHECK(floatRefuses("+"));
+  CHECK(floatRefuses("."));
+  CHECK(floatRefuses("1e"));
+  CHECK(floatRefuses("1e+"));
+  CHECK(floatRefuses("e5"));
+  CHECK(floatRefuses("1e999"));
+  CHECK(floatRefuses("-1e999"));
+  CHECK(floatRefuses("1 2"));
+  CHECK(floatRefuses("infinit"));
+  CHECK(floatRefuses(bytes("1\0" "2", 3)));
+  CHECK(floatRefuses(bytes("inf\0", 4)));
+
+  // ---- the rule of health.interval and the sensors' durations ----
+  auto positive = [](const char* json5, int64_t wantMs) {
+    Duration got{0};
+    return parsePositiveDuration(parseJson5(json5), &got) &&
+           got == std::chrono::milliseconds(wantMs);
+  };
+  auto notPositive = [](const char* json5) {
+    Duration got{0};
+    return !parsePositiveDuration(parseJson5(json5), &got);
+  };
+  CHECK(positive("1", 1000));
+  CHECK(positive("\"1\"", 1000));
+  CHECK(positive("\"500ms\"", 500));
+  CHECK(positive("\"1ms\"", 1));
+  CHECK(positive("\"1m30s\"", 90000));
+  CHECK(notPositive("\"999us\""));
+  CHECK(notPositive("\"0\""));
+  CHECK(notPositive("0"));
+  CHECK(notPositive("-1"));
+  CHECK(notPositive("\"\""));
+  CHECK(notPositive("\"ms\""));
+  CHECK(notPositive("\".5s\""));
+  CHECK(notPositive("\"+5s\""));
+  CHECK(notPositive("\"5\\u00a0s\""));
+  CHECK(notPositive("1.5"));
+  CHECK(notPositive("true"));
+  CHECK(notPositive("null"));
+  CHECK(notPositive("[1]"));
+  CHECK(notPositive("9223372037"));
+  return checks - before;
+}
+
 int main() {
   testJson5();
   testDurations();
@@ -1348,10 +1604,12 @@ int main() {
   testHttpServerRoundTrip();
   testHttpServerBindRetry();
   testUnixPathTooLong();
+  int goTextChecks = testGoText();
   if (failures) {
     fprintf(stderr, "%d failures\n", failures);
     return 1;
   }
-  printf("all unit tests passed\n");
+  printf("all unit tests passed (%d checks, %d of them in testGoText)\n",
+         checks.load(), goTextChecks);
   return 0;
 }
