@@ -12,6 +12,7 @@ build:
 unit: build
 	./bin/cpilot_unittests
 	./bin/cpilot_metricstests tests/golden/metrics_cases.json
+	./bin/cpilot_kvtests
 
 integration: build
 	python3 -m pytest tests/ -q -m "not gpu"
@@ -33,7 +34,7 @@ tsan:
 	  -DCMAKE_CXX_FLAGS="-fsanitize=thread -g -O1"
 	ninja -C build-tsan cpilot_unittests cpilot_probetests \
 	  cpilot_rendertests cpilot_sensortests cpilot_signaltests \
-	  cpilot_metricstests containerpilot cpilot-spawn-helper
+	  cpilot_metricstests cpilot_kvtests containerpilot cpilot-spawn-helper
 	CPILOT_SPAWN_HELPER=build-tsan/bin/cpilot-spawn-helper \
 	  ./build-tsan/bin/cpilot_unittests
 	./build-tsan/bin/cpilot_probetests
@@ -41,6 +42,7 @@ tsan:
 	./build-tsan/bin/cpilot_sensortests
 	./build-tsan/bin/cpilot_signaltests
 	./build-tsan/bin/cpilot_metricstests tests/golden/metrics_cases.json
+	./build-tsan/bin/cpilot_kvtests
 
 asan:
 	cmake -S . -B build-asan -G Ninja -DCMAKE_BUILD_TYPE=RelWithDebInfo \
@@ -48,7 +50,7 @@ asan:
 	  -DCMAKE_CXX_FLAGS="-fsanitize=address,undefined -g -O1"
 	ninja -C build-asan cpilot_unittests cpilot_probetests \
 	  cpilot_rendertests cpilot_sensortests cpilot_signaltests \
-	  cpilot_metricstests containerpilot cpilot-spawn-helper
+	  cpilot_metricstests cpilot_kvtests containerpilot cpilot-spawn-helper
 	CPILOT_SPAWN_HELPER=build-asan/bin/cpilot-spawn-helper \
 	  ./build-asan/bin/cpilot_unittests
 	./build-asan/bin/cpilot_probetests
@@ -56,6 +58,7 @@ asan:
 	./build-asan/bin/cpilot_sensortests
 	./build-asan/bin/cpilot_signaltests
 	./build-asan/bin/cpilot_metricstests tests/golden/metrics_cases.json
+	./build-asan/bin/cpilot_kvtests
 
 soak: build
 	python3 scripts/soak.py 300

@@ -8,17 +8,23 @@ reference calls through the official client — see SURVEY.md §2 #14-15):
   PUT /v1/agent/service/deregister/<serviceID>
   GET /v1/health/service/<name>?passing=1[&tag=..][&dc=..]
 
-Tests drive upstream-change scenarios by mutating `health` and assert on
-`services` / `ttl_updates` / request history. The reference runs a real
+and, for key watches, which the reference does not have:
+
+  GET /v1/kv/<key>[?recurse=true][&dc=..][&index=..&wait=..]
+
+Tests drive upstream-change scenarios by mutating `health` (set_health)
+and `kv` (set_kv, delete_kv) and assert on `services` / `ttl_updates` /
+request history. The reference runs a real
 `consul agent -dev` in its API tests; no consul binary exists in this
 environment so the wire protocol is faked at the HTTP layer instead.
 """
 
+import base64
 import json
 import threading
 import time
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
-from urllib.parse import urlparse, parse_qs
+from urllib.parse import urlparse, parse_qs, unquote
 
 
 class MockConsul:
@@ -29,6 +35,7 @@ class MockConsul:
         self.deregistered = []  # serviceIDs
         self.requests = []      # (method, path)
         self.health = {}        # service name -> list of dicts(ID,Address,Port)
+        self.kv = {}            # key -> (value bytes, flags)
         self.tokens = []        # X-Consul-Token header values seen
         self.fail_mode = False  # when True: every endpoint returns 500
         self.index = 1          # consul-style modify index (global)
@@ -96,6 +103,46 @@ class MockConsul:
                     self.end_headers()
                     self.wfile.write(body)
                     return
+                if parsed.path.startswith("/v1/kv/"):
+                    key = unquote(parsed.path[len("/v1/kv/"):])
+                    qs = parse_qs(parsed.query)
+                    recurse = "recurse" in qs
+                    want_index = int(qs.get("index", ["0"])[0])
+                    wait_s = 0
+                    if "wait" in qs:
+                        wait_s = int(qs["wait"][0].rstrip("s") or 0)
+                    with outer.lock:
+                        if want_index and wait_s:
+                            deadline = time.time() + wait_s
+                            while (outer.index <= want_index and
+                                   time.time() < deadline):
+                                outer.changed.wait(
+                                    max(0.05, deadline - time.time()))
+                        found = sorted(
+                            (k, v) for k, v in outer.kv.items()
+                            if (k.startswith(key) if recurse else k == key))
+                        current_index = outer.index
+                    # a missing key is a 404 with an empty body
+                    body = json.dumps([
+                        {"LockIndex": 0, "Key": k, "Flags": flags,
+                         "Value": (base64.b64encode(value).decode()
+                                   if value else None),
+                         "CreateIndex": 1, "ModifyIndex": current_index}
+                        for k, (value, flags) in found]).encode() \
+                        if found else b""
+                    try:
+                        self.send_response(200 if found else 404)
+                        self.send_header("Content-Type", "application/json")
+                        self.send_header("X-Consul-Index",
+                                         str(current_index))
+                        self.send_header("Content-Length", str(len(body)))
+                        self.end_headers()
+                        self.wfile.write(body)
+                    except (BrokenPipeError, ConnectionResetError):
+                        # the daemon cancelled this long-poll (reload,
+                        # shutdown) or cut an oversized body short
+                        self.close_connection = True
+                    return
                 if parsed.path == "/v1/agent/self":
                     return self._respond(200, b'{"Config":{}}')
                 return self._respond(404, b"not found")
@@ -153,6 +200,18 @@ class MockConsul:
     def set_health(self, service, entries):
         with self.lock:
             self.health[service] = entries
+            self.index += 1
+            self.changed.notify_all()
+
+    def set_kv(self, key, value, flags=0):
+        with self.lock:
+            self.kv[key] = (bytes(value), flags)
+            self.index += 1
+            self.changed.notify_all()
+
+    def delete_kv(self, key):
+        with self.lock:
+            self.kv.pop(key, None)
             self.index += 1
             self.changed.notify_all()
 

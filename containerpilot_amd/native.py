@@ -5,6 +5,7 @@ engine, JSON5 parser, duration rules, config validation).
 """
 
 import ctypes
+import json
 import os
 
 from . import REPO_ROOT
@@ -46,6 +47,16 @@ def _load():
         _lib.cp_watch_render.argtypes = [
             ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p,
             ctypes.c_char_p, ctypes.c_char_p,
+            ctypes.POINTER(ctypes.c_void_p)]
+        _lib.cp_kv_decode.restype = ctypes.c_void_p
+        _lib.cp_kv_decode.argtypes = [
+            ctypes.c_char_p, ctypes.c_size_t,
+            ctypes.POINTER(ctypes.c_void_p)]
+        _lib.cp_kv_render.restype = ctypes.c_void_p
+        _lib.cp_kv_render.argtypes = [
+            ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t,
+            ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int,
+            ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t),
             ctypes.POINTER(ctypes.c_void_p)]
         _lib.cp_sensor_extract.restype = ctypes.c_int
         _lib.cp_sensor_extract.argtypes = [
@@ -188,6 +199,43 @@ def watch_render(template_text, health_body_json, name, tag="", dc=""):
     if not out:
         raise ValueError(_take_string(lib, err.value))
     return _take_string(lib, out)
+
+
+def kv_decode(body):
+    """Decode a /v1/kv response body (str or bytes) the way a key watch
+    does: a list of {"Key", "ValueHex", "Flags"} sorted by key, the value
+    as hex so it stays byte-exact. Raises ValueError on what the daemon
+    treats as a failed query."""
+    lib = _load()
+    if isinstance(body, str):
+        body = body.encode()
+    err = ctypes.c_void_p()
+    out = lib.cp_kv_decode(body, len(body), ctypes.byref(err))
+    if not out:
+        raise ValueError(_take_string(lib, err.value))
+    return json.loads(_take_string(lib, out))
+
+
+def kv_render(template_text, body, name, key, prefix=False, dc=""):
+    """Dry-run of a key watch's `render`: the bytes the daemon would write
+    for the raw /v1/kv response body `body` (str or bytes; None stands for
+    the 404 of a missing key) of watch `name` on `key`, or on the prefix
+    `key` when `prefix` is set. Returns bytes, since values pass through
+    unchanged. Raises ValueError on a bad body or a template error."""
+    lib = _load()
+    if isinstance(body, str):
+        body = body.encode()
+    err = ctypes.c_void_p()
+    size = ctypes.c_size_t()
+    out = lib.cp_kv_render(template_text.encode(), body,
+                           len(body) if body is not None else 0,
+                           name.encode(), key.encode(), int(bool(prefix)),
+                           dc.encode(), ctypes.byref(size), ctypes.byref(err))
+    if not out:
+        raise ValueError(_take_string(lib, err.value))
+    rendered = ctypes.string_at(out, size.value)
+    lib.cp_free(out)
+    return rendered
 
 
 def metrics_replay(script_json):

@@ -18,6 +18,7 @@
 
 #include "cpilot/http.hpp"
 #include "cpilot/json.hpp"
+#include "cpilot/kv.hpp"
 #include "cpilot/loop.hpp"
 #include "cpilot/metrics.hpp"
 
@@ -37,6 +38,14 @@ struct ServiceEntry {
 // object are skipped; a body that does not parse clears *ok.
 std::vector<ServiceEntry> parseHealthEntries(const std::string& body,
                                              bool* ok);
+
+// The request target of a KV query: /v1/kv/<key> with, in this order and
+// each only when it applies, recurse=true (prefix), dc=<dc> and
+// index=<n>&wait=<s>s (blocking). '/' stays '/' in the key; every other
+// byte is encoded as in the other Consul paths.
+std::string kvRequestPath(const std::string& key, bool prefix,
+                          const std::string& dc, bool blocking = false,
+                          uint64_t index = 0, int waitSeconds = 0);
 
 class ConsulBackend {
  public:
@@ -85,6 +94,24 @@ class ConsulBackend {
   bool compareAndSwap(const std::string& service,
                       std::vector<ServiceEntry> entries);
 
+  // Key watches. ok is false for a failed query; a 404 is a successful
+  // result with zero entries.
+  using KVCb = std::function<void(bool ok, std::vector<KVEntry> entries)>;
+  using KVBlockingCb = std::function<void(
+      bool ok, std::vector<KVEntry> entries, uint64_t index)>;
+  // GET /v1/kv/<key> (see kvRequestPath), polled through the worker pool
+  void kvGet(const std::string& key, bool prefix, const std::string& dc,
+             KVCb cb);
+  // the long-polling variant: own thread, cancellable, like
+  // healthServiceBlocking
+  void kvGetBlocking(const std::string& key, bool prefix,
+                     const std::string& dc, uint64_t lastIndex,
+                     int waitSeconds, KVBlockingCb cb);
+  // change detection for key watches against the set cached under the
+  // watch's name (loop thread only); `entries` sorted by key
+  bool compareAndSwapKV(const std::string& watch,
+                        std::vector<KVEntry> entries);
+
   const std::string& address() const { return address_; }
   const std::string& scheme() const { return scheme_; }
 
@@ -99,6 +126,16 @@ class ConsulBackend {
   // Returns false when rejected; callers must complete their callback
   // path themselves (in-flight guards would otherwise stick).
   bool enqueue(const std::string& key, std::function<void()> task);
+  // The shared part of the blocking queries: GET `path` on a short-lived
+  // cancellable thread of its own, registered so stop() can interrupt it.
+  // `finish` runs on that thread with the response, whether the query is
+  // still live (not cancelled) and the X-Consul-Index it carried, and
+  // returns what is then posted onto the reactor. Returns false, starting
+  // nothing, once the backend is stopping.
+  using BlockingFinish = std::function<std::function<void()>(
+      const http::ClientResult& res, bool live, uint64_t index)>;
+  bool startBlockingGet(const std::string& path, int waitSeconds,
+                        size_t maxBody, BlockingFinish finish);
 
   std::string address_;  // host:port
   std::string scheme_ = "http";
@@ -115,6 +152,7 @@ class ConsulBackend {
   bool stopping_ = false;
 
   std::map<std::string, std::vector<ServiceEntry>> watched_;
+  std::map<std::string, std::vector<KVEntry>> watchedKV_;  // by watch name
   std::shared_ptr<prom::Family> watchGauge_;
 
   // blocking queries run on their own short-lived threads (a parked

@@ -2,10 +2,13 @@
 // seconds; on membership/address change publish StatusChanged plus
 // StatusHealthy/StatusUnhealthy from source "watch.<name>".
 // Parity: /root/reference/watches/{watches,config}.go.
+// extension: a watch with `key` or `keyPrefix` watches Consul's key/value
+// store instead (cpilot/kv.hpp); events, render and scheduling are shared.
 #pragma once
 
 #include <sys/types.h>
 
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -39,6 +42,11 @@ struct WatchConfig {
   // window. `interval` becomes the error-backoff period.
   bool blocking = false;
   std::shared_ptr<RenderConfig> render;  // null when not configured
+  // extension: a key watch. `key` holds watches[].key or, with keyPrefix
+  // set, watches[].keyPrefix; serviceName is then only the event source.
+  bool isKey = false;
+  bool keyPrefix = false;
+  std::string key;
 };
 
 // Decodes and validates shape only; never touches the filesystem.
@@ -73,7 +81,10 @@ class Watch : public std::enable_shared_from_this<Watch> {
         dc_(cfg->dc),
         poll_(cfg->poll),
         blocking_(cfg->blocking),
-        render_(cfg->render) {}
+        render_(cfg->render),
+        isKey_(cfg->isKey),
+        keyPrefix_(cfg->keyPrefix),
+        key_(cfg->key) {}
 
   const std::string& name() const { return name_; }
   const std::string& serviceName() const { return serviceName_; }
@@ -84,13 +95,21 @@ class Watch : public std::enable_shared_from_this<Watch> {
  private:
   void tick();
   void issueBlocking();
+  void afterBlocking(bool ok, uint64_t index);
   void onResult(bool ok, std::vector<ServiceEntry> entries);
-  bool renderDest(const std::vector<ServiceEntry>& entries, std::string* err);
+  void onKVResult(bool ok, std::vector<KVEntry> entries);
+  // the part both kinds of watch share: render, then the events
+  void publishResult(bool didChange, bool isHealthy,
+                     const std::function<Json()>& renderData);
+  bool renderDest(const Json& data, std::string* err);
 
   std::string name_, serviceName_, tag_, dc_;
   int poll_;
   bool blocking_ = false;
   std::shared_ptr<RenderConfig> render_;
+  bool isKey_ = false;
+  bool keyPrefix_ = false;
+  std::string key_;
   bool rendered_ = false;  // first successful result seen this generation
   uint64_t lastIndex_ = 0;
   Loop* loop_ = nullptr;

@@ -409,14 +409,27 @@ void ConsulBackend::healthServiceBlocking(const std::string& name,
   if (!dc.empty()) path += "&dc=" + urlEncode(dc);
   path += "&index=" + std::to_string(lastIndex) +
           "&wait=" + std::to_string(waitSeconds) + "s";
+  bool started = startBlockingGet(
+      path, waitSeconds, 0,
+      [cb](const http::ClientResult& res, bool live,
+           uint64_t index) -> std::function<void()> {
+        bool ok = res.ok && res.status == 200 && live;
+        std::vector<ServiceEntry> entries;
+        if (ok) entries = parseHealthEntries(res.body, &ok);
+        return [cb, ok, index, entries = std::move(entries)]() mutable {
+          cb(ok, std::move(entries), index);
+        };
+      });
+  if (!started) loop_->post([cb] { cb(false, {}, 0); });
+}
+
+bool ConsulBackend::startBlockingGet(const std::string& path, int waitSeconds,
+                                     size_t maxBody, BlockingFinish finish) {
   auto token = std::make_shared<http::CancelToken>();
   auto reg = blockingReg_;
   {
     std::lock_guard<std::mutex> l(reg->mu);
-    if (reg->stopping) {
-      loop_->post([cb] { cb(false, {}, 0); });
-      return;
-    }
+    if (reg->stopping) return false;
     reg->tokens.insert(token);
   }
   std::string target = address_;
@@ -427,29 +440,114 @@ void ConsulBackend::healthServiceBlocking(const std::string& name,
   // blocking watches would starve TTL heartbeats), so each query gets a
   // short-lived thread of its own; `this` is NOT captured — the thread
   // may outlive the backend and touches only the shared reg + the loop
-  std::thread([reg, target, tokenHdr, tls, path, cb, loop, token,
-               waitSeconds] {
+  std::thread([reg, target, tokenHdr, tls, path, finish, loop, token,
+               waitSeconds, maxBody] {
     resetThreadScheduling();
     std::map<std::string, std::string> headers;
     if (!tokenHdr.empty()) headers["X-Consul-Token"] = tokenHdr;
     auto res = http::request(target, "GET", path, "", "application/json",
                              headers, (waitSeconds + 10) * 1000, &tls,
-                             token.get());
+                             token.get(), maxBody);
     {
       std::lock_guard<std::mutex> l(reg->mu);
       reg->tokens.erase(token);
     }
-    bool ok = res.ok && res.status == 200 && !token->cancelled();
     uint64_t index = 0;
     auto it = res.headers.find("x-consul-index");
     if (it != res.headers.end())
       index = strtoull(it->second.c_str(), nullptr, 10);
-    std::vector<ServiceEntry> entries;
-    if (ok) entries = parseHealthEntries(res.body, &ok);
-    loop->post([cb, ok, index, entries = std::move(entries)]() mutable {
-      cb(ok, std::move(entries), index);
-    });
+    loop->post(finish(res, !token->cancelled(), index));
   }).detach();
+  return true;
+}
+
+std::string kvRequestPath(const std::string& key, bool prefix,
+                          const std::string& dc, bool blocking,
+                          uint64_t index, int waitSeconds) {
+  std::string path = "/v1/kv/";
+  size_t start = 0;
+  while (true) {
+    size_t slash = key.find('/', start);
+    path += urlEncode(key.substr(start, slash - start));
+    if (slash == std::string::npos) break;
+    path += '/';
+    start = slash + 1;
+  }
+  char sep = '?';
+  auto add = [&](const std::string& param) {
+    path += sep + param;
+    sep = '&';
+  };
+  if (prefix) add("recurse=true");
+  if (!dc.empty()) add("dc=" + urlEncode(dc));
+  if (blocking)
+    add("index=" + std::to_string(index) +
+        "&wait=" + std::to_string(waitSeconds) + "s");
+  return path;
+}
+
+namespace {
+
+// 200 with a well-formed body, or 404 (no such key, nothing under the
+// prefix: zero entries); anything else is a failed query
+bool kvResult(const http::ClientResult& res, std::vector<KVEntry>* entries) {
+  entries->clear();
+  if (!res.ok) return false;
+  if (res.status == 404) return true;
+  return res.status == 200 && parseKVEntries(res.body, entries);
+}
+
+}  // namespace
+
+void ConsulBackend::kvGet(const std::string& key, bool prefix,
+                          const std::string& dc, KVCb cb) {
+  std::string path = kvRequestPath(key, prefix, dc);
+  std::string target = address_;
+  std::string token = token_;
+  http::TlsOptions tls = tls_;
+  Loop* loop = loop_;
+  bool accepted = enqueue(
+      std::string("kv:") + (prefix ? "prefix|" : "key|") + key + "|" + dc,
+      [target, token, tls, path, cb, loop] {
+        std::map<std::string, std::string> headers;
+        if (!token.empty()) headers["X-Consul-Token"] = token;
+        auto res = http::request(target, "GET", path, "", "application/json",
+                                 headers, 10000, &tls, nullptr, kKVMaxBody);
+        std::vector<KVEntry> entries;
+        bool ok = kvResult(res, &entries);
+        loop->post(timedItem(
+            "consul", [cb, ok, entries = std::move(entries)]() mutable {
+              cb(ok, std::move(entries));
+            }));
+      });
+  if (!accepted) {
+    loop_->post([cb] { cb(false, {}); });
+  }
+}
+
+void ConsulBackend::kvGetBlocking(const std::string& key, bool prefix,
+                                  const std::string& dc, uint64_t lastIndex,
+                                  int waitSeconds, KVBlockingCb cb) {
+  bool started = startBlockingGet(
+      kvRequestPath(key, prefix, dc, true, lastIndex, waitSeconds),
+      waitSeconds, kKVMaxBody,
+      [cb](const http::ClientResult& res, bool live,
+           uint64_t index) -> std::function<void()> {
+        std::vector<KVEntry> entries;
+        bool ok = live && kvResult(res, &entries);
+        return [cb, ok, index, entries = std::move(entries)]() mutable {
+          cb(ok, std::move(entries), index);
+        };
+      });
+  if (!started) loop_->post([cb] { cb(false, {}, 0); });
+}
+
+bool ConsulBackend::compareAndSwapKV(const std::string& watch,
+                                     std::vector<KVEntry> entries) {
+  std::vector<KVEntry>& cached = watchedKV_[watch];
+  bool changed = kvEntriesDiffer(cached, entries);
+  cached = std::move(entries);
+  return changed;
 }
 
 bool ConsulBackend::compareAndSwap(const std::string& service,

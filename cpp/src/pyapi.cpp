@@ -151,6 +151,65 @@ char* cp_watch_render(const char* templateText, const char* healthBodyJson,
   }
 }
 
+// Decode a /v1/kv response body (bodyLen bytes) the way a key watch does.
+// Returns a JSON list of {"Key", "ValueHex", "Flags"} sorted by key, the
+// value as lower-case hex so it stays byte-exact; nullptr + *errOut on
+// what the daemon treats as a failed query.
+char* cp_kv_decode(const char* body, size_t bodyLen, char** errOut) {
+  try {
+    std::vector<KVEntry> entries;
+    if (!parseKVEntries(std::string(body, bodyLen), &entries)) {
+      if (errOut) *errOut = dupString("could not parse kv response body");
+      return nullptr;
+    }
+    JsonArray rows;
+    for (auto& e : entries) {
+      std::string hex;
+      for (unsigned char c : e.value) {
+        const char* digits = "0123456789abcdef";
+        hex += digits[c >> 4];
+        hex += digits[c & 15];
+      }
+      rows.push_back(Json(JsonObject{{"Key", Json(e.key)},
+                                     {"ValueHex", Json(std::move(hex))},
+                                     {"Flags", Json((int64_t)e.flags)}}));
+    }
+    return dupString(Json(std::move(rows)).dump());
+  } catch (const std::exception& e) {
+    if (errOut) *errOut = dupString(e.what());
+    return nullptr;
+  }
+}
+
+// Dry-run of a key watch's `render`: decode `body` (bodyLen bytes; nullptr
+// stands for the 404 of a missing key) the way the daemon does, build the
+// data model of watch `name` on `key` (a prefix when `prefix` is non-zero)
+// and render `templateText` against it. The rendering may hold any byte:
+// returns a malloc'd buffer of *outLen bytes; nullptr + *errOut on a bad
+// body or a template error.
+char* cp_kv_render(const char* templateText, const char* body, size_t bodyLen,
+                   const char* name, const char* key, int prefix,
+                   const char* dc, size_t* outLen, char** errOut) {
+  try {
+    std::vector<KVEntry> entries;
+    if (body && !parseKVEntries(std::string(body, bodyLen), &entries)) {
+      if (errOut) *errOut = dupString("could not parse kv response body");
+      return nullptr;
+    }
+    Template tmpl = Template::parse(templateText);
+    std::string out = tmpl.render(
+        buildKVRenderData(name, key, prefix != 0, dc ? dc : "", entries));
+    char* buf = (char*)malloc(out.size() + 1);
+    memcpy(buf, out.data(), out.size());
+    buf[out.size()] = '\0';
+    if (outLen) *outLen = out.size();
+    return buf;
+  } catch (const std::exception& e) {
+    if (errOut) *errOut = dupString(e.what());
+    return nullptr;
+  }
+}
+
 // Dry-run of one sensor `record`: extract the number from `body` (bodyLen
 // bytes, NULs allowed) the way the daemon does and apply the scale. The
 // metric named by the record is not looked up.

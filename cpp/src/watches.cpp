@@ -99,7 +99,9 @@ bool newWatchConfigs(const Json& rawWatches,
       return false;
     }
     if (!decode::checkKeys(
-            raw, {"name", "interval", "tag", "dc", "blocking", "render"},
+            raw,
+            {"name", "interval", "tag", "dc", "blocking", "render", "key",
+             "keyPrefix"},
             err)) {
       *err = "Watch configuration error: " + *err;
       return false;
@@ -119,6 +121,29 @@ bool newWatchConfigs(const Json& rawWatches,
     if (!validateServiceName(cfg->name, err)) return false;
     cfg->serviceName = cfg->name;
     cfg->name = "watch." + cfg->name;  // watches/config.go:44-45
+    // a key watch: `key` or `keyPrefix`, null counting as not given
+    const Json* key = decode::given(raw, "key");
+    const Json* keyPrefix = decode::given(raw, "keyPrefix");
+    if (key && keyPrefix) {
+      *err = "watch[" + cfg->serviceName +
+             "]: key and keyPrefix are mutually exclusive";
+      return false;
+    }
+    if (key || keyPrefix) {
+      const char* field = key ? "key" : "keyPrefix";
+      std::string why;
+      if (!validateKVKey(key ? *key : *keyPrefix, &cfg->key, &why)) {
+        *err = "watch[" + cfg->serviceName + "]." + field + " " + why;
+        return false;
+      }
+      if (decode::given(raw, "tag")) {
+        *err = "watch[" + cfg->serviceName +
+               "].tag does not apply to a key watch";
+        return false;
+      }
+      cfg->isKey = true;
+      cfg->keyPrefix = keyPrefix != nullptr;
+    }
     if (cfg->poll < 1) {
       *err = "watch[" + cfg->serviceName + "].interval must be > 0";
       return false;
@@ -129,6 +154,18 @@ bool newWatchConfigs(const Json& rawWatches,
         return false;
     }
     out->push_back(cfg);
+  }
+  // a key watch's name is its cache key and its only identity: it must be
+  // the only watch of that name. Service watches keep what they did.
+  for (auto& a : *out) {
+    if (!a->isKey) continue;
+    for (auto& b : *out) {
+      if (a != b && a->name == b->name) {
+        *err = "watch[" + a->serviceName +
+               "]: a key watch must not share its name with another watch";
+        return false;
+      }
+    }
   }
   return true;
 }
@@ -253,13 +290,33 @@ void Watch::onResult(bool ok, std::vector<ServiceEntry> entries) {
   consul_->watchGauge()->set({serviceName_}, (double)entries.size());
   bool isHealthy = !entries.empty();
   bool didChange = consul_->compareAndSwap(serviceName_, entries);
+  publishResult(didChange, isHealthy, [&] {
+    return buildRenderData(serviceName_, tag_, dc_, entries);
+  });
+}
+
+void Watch::onKVResult(bool ok, std::vector<KVEntry> entries) {
+  if (!ok) {
+    LOG_WARN("failed to query key %s", key_.c_str());
+    return;
+  }
+  // healthy: the key exists, or something lies under the prefix
+  bool isHealthy = !entries.empty();
+  bool didChange = consul_->compareAndSwapKV(serviceName_, entries);
+  publishResult(didChange, isHealthy, [&] {
+    return buildKVRenderData(serviceName_, key_, keyPrefix_, dc_, entries);
+  });
+}
+
+void Watch::publishResult(bool didChange, bool isHealthy,
+                          const std::function<Json()>& renderData) {
   // the file is in place before anything hears about this result; the
   // first result of a generation renders even when nothing changed, so
   // dest exists before anything depends on it
   if (render_ && (didChange || !rendered_)) {
     rendered_ = true;
     std::string err;
-    if (!renderDest(entries, &err)) {
+    if (!renderDest(renderData(), &err)) {
       LOG_ERROR("%s: render: %s", name_.c_str(), err.c_str());
       bus_->publish(Event{EventCode::Error, name_ + ": render: " + err});
     }
@@ -273,12 +330,10 @@ void Watch::onResult(bool ok, std::vector<ServiceEntry> entries) {
   }
 }
 
-bool Watch::renderDest(const std::vector<ServiceEntry>& entries,
-                       std::string* err) {
+bool Watch::renderDest(const Json& data, std::string* err) {
   std::string out;
   try {
-    out = render_->tmpl.render(
-        buildRenderData(serviceName_, tag_, dc_, entries));
+    out = render_->tmpl.render(data);
   } catch (const std::exception& e) {
     *err = e.what();
     return false;
@@ -291,6 +346,15 @@ void Watch::tick() {
   if (inFlight_) return;  // one query at a time; skip this tick
   inFlight_ = true;
   auto self = shared_from_this();
+  if (isKey_) {
+    consul_->kvGet(key_, keyPrefix_, dc_,
+                   [this, self](bool ok, std::vector<KVEntry> entries) {
+                     inFlight_ = false;
+                     if (stopped_) return;
+                     onKVResult(ok, std::move(entries));
+                   });
+    return;
+  }
   consul_->healthService(
       serviceName_, tag_, dc_,
       [this, self](bool ok, std::vector<ServiceEntry> entries) {
@@ -303,25 +367,40 @@ void Watch::tick() {
 void Watch::issueBlocking() {
   if (stopped_ || !consul_) return;
   auto self = shared_from_this();
+  if (isKey_) {
+    consul_->kvGetBlocking(
+        key_, keyPrefix_, dc_, lastIndex_, 10,
+        [this, self](bool ok, std::vector<KVEntry> entries, uint64_t index) {
+          if (stopped_) return;
+          onKVResult(ok, std::move(entries));
+          afterBlocking(ok, index);
+        });
+    return;
+  }
   consul_->healthServiceBlocking(
       serviceName_, tag_, dc_, lastIndex_, 10,
       [this, self](bool ok, std::vector<ServiceEntry> entries,
                    uint64_t index) {
         if (stopped_) return;
         onResult(ok, std::move(entries));
-        if (ok) {
-          // consul index contract: reset when it goes backwards
-          lastIndex_ = (index > 0 && index >= lastIndex_) ? index : 0;
-          // immediate re-issue with a tiny floor so a hot agent can't
-          // spin us
-          timer_ = loop_->addTimeout(std::chrono::milliseconds(50),
-                                     [this, self] { issueBlocking(); });
-        } else {
-          // error backoff: fall back to the configured interval
-          timer_ = loop_->addTimeout(std::chrono::seconds(poll_),
-                                     [this, self] { issueBlocking(); });
-        }
+        afterBlocking(ok, index);
       });
+}
+
+void Watch::afterBlocking(bool ok, uint64_t index) {
+  auto self = shared_from_this();
+  if (ok) {
+    // consul index contract: reset when it goes backwards
+    lastIndex_ = (index > 0 && index >= lastIndex_) ? index : 0;
+    // immediate re-issue with a tiny floor so a hot agent can't
+    // spin us
+    timer_ = loop_->addTimeout(std::chrono::milliseconds(50),
+                               [this, self] { issueBlocking(); });
+  } else {
+    // error backoff: fall back to the configured interval
+    timer_ = loop_->addTimeout(std::chrono::seconds(poll_),
+                               [this, self] { issueBlocking(); });
+  }
 }
 
 }  // namespace cpilot
