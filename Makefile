@@ -34,7 +34,8 @@ tsan:
 	  -DCMAKE_CXX_FLAGS="-fsanitize=thread -g -O1"
 	ninja -C build-tsan cpilot_unittests cpilot_probetests \
 	  cpilot_rendertests cpilot_sensortests cpilot_signaltests \
-	  cpilot_metricstests cpilot_kvtests containerpilot cpilot-spawn-helper
+	  cpilot_metricstests cpilot_kvtests cpilot_httpjobtests containerpilot \
+	  cpilot-spawn-helper
 	CPILOT_SPAWN_HELPER=build-tsan/bin/cpilot-spawn-helper \
 	  ./build-tsan/bin/cpilot_unittests
 	./build-tsan/bin/cpilot_probetests
@@ -43,6 +44,7 @@ tsan:
 	./build-tsan/bin/cpilot_signaltests
 	./build-tsan/bin/cpilot_metricstests tests/golden/metrics_cases.json
 	./build-tsan/bin/cpilot_kvtests
+	./build-tsan/bin/cpilot_httpjobtests
 
 asan:
 	cmake -S . -B build-asan -G Ninja -DCMAKE_BUILD_TYPE=RelWithDebInfo \
@@ -50,7 +52,8 @@ asan:
 	  -DCMAKE_CXX_FLAGS="-fsanitize=address,undefined -g -O1"
 	ninja -C build-asan cpilot_unittests cpilot_probetests \
 	  cpilot_rendertests cpilot_sensortests cpilot_signaltests \
-	  cpilot_metricstests cpilot_kvtests containerpilot cpilot-spawn-helper
+	  cpilot_metricstests cpilot_kvtests cpilot_httpjobtests containerpilot \
+	  cpilot-spawn-helper
 	CPILOT_SPAWN_HELPER=build-asan/bin/cpilot-spawn-helper \
 	  ./build-asan/bin/cpilot_unittests
 	./build-asan/bin/cpilot_probetests
@@ -59,6 +62,7 @@ asan:
 	./build-asan/bin/cpilot_signaltests
 	./build-asan/bin/cpilot_metricstests tests/golden/metrics_cases.json
 	./build-asan/bin/cpilot_kvtests
+	./build-asan/bin/cpilot_httpjobtests
 
 soak: build
 	python3 scripts/soak.py 300

@@ -66,6 +66,10 @@ def _load():
         _lib.cp_signal_number.restype = ctypes.c_int
         _lib.cp_signal_number.argtypes = [
             ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
+        _lib.cp_http_action_request.restype = ctypes.c_void_p
+        _lib.cp_http_action_request.argtypes = [
+            ctypes.c_char_p, ctypes.POINTER(ctypes.c_size_t),
+            ctypes.POINTER(ctypes.c_void_p)]
         _lib.cp_metrics_replay.restype = ctypes.c_void_p
         _lib.cp_metrics_replay.argtypes = [
             ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
@@ -185,6 +189,23 @@ def signal_number(name):
     if signo < 0:
         raise ValueError(_take_string(lib, err.value))
     return signo
+
+
+def http_action_request(job_json):
+    """The exact bytes the http job `job_json` (one entry of `jobs`, as JSON
+    text) writes to its target: request line, headers and body. Raises
+    ValueError with the config error of a refused job, or for a job that
+    has no `http`."""
+    lib = _load()
+    err = ctypes.c_void_p()
+    size = ctypes.c_size_t()
+    out = lib.cp_http_action_request(job_json.encode(), ctypes.byref(size),
+                                     ctypes.byref(err))
+    if not out:
+        raise ValueError(_take_string(lib, err.value))
+    request = ctypes.string_at(out, size.value)
+    lib.cp_free(out)
+    return request
 
 
 def watch_render(template_text, health_body_json, name, tag="", dc=""):

@@ -55,6 +55,10 @@ struct JobConfig {
   std::string name;
   CommandPtr exec;
   std::shared_ptr<SignalAction> signal;
+  // A job whose action is an HTTP request (`http`, exclusive with `exec`
+  // and `signal`): the probe engine in its action mode, publishing from
+  // source `<job>`.
+  health::ProbePtr http;
 
   // service discovery
   int port = 0;
@@ -106,7 +110,8 @@ class Job : public Subscriber, public std::enable_shared_from_this<Job> {
   void run(Loop& loop, std::shared_ptr<Bus> bus,
            std::function<void()> completedCb);
 
-  // SIGKILL the exec's process group (kill sweep, core/app.go:152-155)
+  // SIGKILL the exec's process group (kill sweep, core/app.go:152-155);
+  // an http request in flight is canceled
   void kill();
 
   void onEvent(const Event& event) override;
@@ -142,8 +147,11 @@ class Job : public Subscriber, public std::enable_shared_from_this<Job> {
   // signal jobs: deliver on the reactor, then publish the exit event an
   // exec that finished at once would have produced
   void runSignalAction();
+  void runHttpAction();
   void endSignalWait(bool targetExited);
-  bool ignoredDuringSignalWait() const;
+  // a start that finds the job's own action (a signal's `wait`, an http
+  // request) still in flight
+  bool ignoredWhileInFlight() const;
   void setStatus(JobStatus s);
   void checkRegistration();
   void sendHeartbeat();
@@ -161,6 +169,7 @@ class Job : public Subscriber, public std::enable_shared_from_this<Job> {
   std::shared_ptr<SignalAction> signal_;
   size_t hSignalTarget_ = 0;
   bool signalWaiting_ = false;  // delivered, `wait` pending
+  health::ProbePtr http_;
   JobStatus status_ = JobStatus::Idle;
   std::shared_ptr<ServiceDefinition> service_;
   CommandPtr healthCheckExec_;

@@ -7,6 +7,10 @@
 // A probe publishes the same verdict events an exec check does
 // (ExitSuccess / ExitFailed + Error, source `check.<job>`), so Job,
 // `when:` sources and the events counter need no new cases.
+//
+// The same engine runs http jobs (`jobs[].http`): a request that may carry
+// a body, published from source `<job>`, which reads the response out
+// instead of resetting the connection at the status line.
 #pragma once
 
 #include <sys/socket.h>
@@ -34,6 +38,13 @@ extern const char* const kProbeClosedEarly;
 
 // Response bytes accepted while looking for the status line's CRLF.
 constexpr size_t kProbeMaxStatusLine = 8192;
+// Longest `body` an http job may send.
+constexpr size_t kActionMaxBody = 65536;
+// Response bytes an http job reads and discards before it stops waiting
+// for the peer to finish.
+constexpr size_t kActionMaxDrain = 1024 * 1024;
+// Response head an http job buffers while looking for a Content-Length.
+constexpr size_t kActionMaxHead = 64 * 1024;
 
 struct ProbeSpec {
   enum class Kind { Tcp, Http };
@@ -52,6 +63,14 @@ struct ProbeSpec {
   std::vector<std::pair<std::string, std::string>> headers;
   std::vector<int> expect;  // empty = any 2xx
 
+  // http jobs only: the request is the job's action, not a check. It may
+  // carry a body, it is logged as an action, and the response is read out
+  // and discarded instead of reset at the status line.
+  bool action = false;
+  std::string url;  // as configured, for log lines
+  bool hasBody = false;
+  std::string body;
+
   Duration timeout{0};
 };
 
@@ -66,7 +85,13 @@ bool parseTcpProbe(const std::string& hostPort, ProbeSpec* out,
 bool parseHttpProbe(const Json& raw, ProbeSpec* out, std::string* errKey,
                     std::string* err);
 
-// The exact request bytes an http probe writes.
+// Parse `jobs[].http`: a URL string or {url, method, headers, expect,
+// body}. The rules of `health.http` plus the methods that change state, a
+// body for them, and a refusal of the headers the daemon sets itself.
+bool parseHttpAction(const Json& raw, ProbeSpec* out, std::string* errKey,
+                     std::string* err);
+
+// The exact request bytes an http probe or an http job writes.
 std::string buildProbeRequest(const ProbeSpec& spec);
 
 // "1s", "250ms", "1500ms", "10us", "7ns": the largest unit that divides
@@ -97,7 +122,7 @@ class Probe : public std::enable_shared_from_this<Probe> {
   bool running() const { return state_ != State::Idle; }
 
  private:
-  enum class State { Idle, Connecting, Sending, Reading };
+  enum class State { Idle, Connecting, Sending, Reading, Draining };
 
   void onIo(uint32_t events);
   void onConnected();
@@ -105,8 +130,14 @@ class Probe : public std::enable_shared_from_this<Probe> {
   void onReadable();
   void onTimeout();
   void judgeStatusLine(size_t crlf);
-  // release the socket and the timer; returns the bus of this run
-  std::shared_ptr<Bus> teardown();
+  // actions: hold the verdict and read the response out
+  void beginDrain(size_t crlf);
+  void onDrainReadable();
+  bool drainComplete();
+  void finishDrain(bool peerClosed);
+  // release the socket and the timer; returns the bus of this run. The
+  // close is abortive unless `orderly`.
+  std::shared_ptr<Bus> teardown(bool orderly = false);
   void pass();
   void fail(const std::string& reason, bool timedOut = false);
   void failErrno(int err);
@@ -122,6 +153,14 @@ class Probe : public std::enable_shared_from_this<Probe> {
   uint64_t timer_ = 0;
   size_t sent_ = 0;
   std::string rbuf_;
+
+  // the verdict of the status line, held while an action drains
+  int code_ = 0;
+  std::string verdict_;  // empty = passed
+  size_t drained_ = 0;   // response bytes read so far
+  bool headDone_ = false;
+  bool bodyKnown_ = false;  // the head announced a length
+  size_t bodyEnd_ = 0;      // drained_ at which that length has arrived
 };
 
 using ProbePtr = std::shared_ptr<Probe>;

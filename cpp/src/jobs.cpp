@@ -464,18 +464,49 @@ bool validateSignal(const Json& raw, std::shared_ptr<JobConfig>& cfg,
   return true;
 }
 
-// a restart of an action that finishes at once is a busy loop: only
-// `when.interval` paces it (call after validateWhen and validateRestarts)
-bool validateSignalRestarts(const Json* restarts,
+// http{} block: a job whose action is an HTTP request, run on the reactor
+// by the probe engine. Parses into `spec`; validateJobConfig builds the
+// action once the job's timeout is known.
+bool validateHttp(const Json& raw, std::shared_ptr<JobConfig>& cfg,
+                  health::ProbeSpec* spec, bool* given, std::string* err) {
+  const Json* http = raw.find("http");
+  *given = http && !http->isNull();
+  if (!*given) return true;
+  for (const char* key : {"exec", "signal"}) {
+    if (decode::given(raw, key)) {
+      *err = "job[" + cfg->name + "].http cannot be combined with '" + key +
+             "'";
+      return false;
+    }
+  }
+  // no child, no output and nothing to register
+  for (const char* key : {"port", "health", "logging"}) {
+    if (decode::given(raw, key)) {
+      *err = "job[" + cfg->name + "].http cannot be combined with '" + key +
+             "': an http job starts no process";
+      return false;
+    }
+  }
+  std::string key, specErr;
+  if (!health::parseHttpAction(*http, spec, &key, &specErr)) {
+    *err = "job[" + cfg->name + "].http" + key + ": " + specErr;
+    return false;
+  }
+  return true;
+}
+
+// a restart of an action that finishes at once (a signal, a refused
+// connection) is a busy loop: only `when.interval` paces it (call after
+// validateWhen and validateRestarts)
+bool validateActionRestarts(const Json* restarts, const char* action,
                             const std::shared_ptr<JobConfig>& cfg,
                             std::string* err) {
-  if (!cfg->signal || cfg->freqInterval > Duration(0) ||
-      cfg->restartLimit == 0)
-    return true;
+  if (cfg->freqInterval > Duration(0) || cfg->restartLimit == 0) return true;
   std::string rendered =
       restarts->isString() ? restarts->str() : restarts->dump();
-  *err = "job[" + cfg->name + "].signal cannot be combined with restarts '" +
-         rendered + "' unless 'when.interval' is set";
+  *err = "job[" + cfg->name + "]." + action +
+         " cannot be combined with restarts '" + rendered +
+         "' unless 'when.interval' is set";
   return false;
 }
 
@@ -491,7 +522,7 @@ bool validateJobConfig(const Json& raw, ConsulBackend* disc,
           raw,
           {"name", "exec", "port", "initial_status", "interfaces", "tags",
            "consul", "health", "timeout", "restarts", "stopTimeout", "when",
-           "logging", "signal"},
+           "logging", "signal", "http"},
           err)) {
     *err = "job configuration error: " + *err;
     return false;
@@ -524,6 +555,9 @@ bool validateJobConfig(const Json& raw, ConsulBackend* disc,
     }
   }
 
+  health::ProbeSpec httpSpec;
+  bool httpGiven = false;
+  if (!validateHttp(raw, cfg, &httpSpec, &httpGiven, err)) return false;
   if (!validateSignal(raw, cfg, err)) return false;
   // order mirrors Config.Validate (jobs/config.go:118-133)
   if (!validateDiscovery(raw, disc, cfg, err)) return false;
@@ -542,8 +576,22 @@ bool validateJobConfig(const Json& raw, ConsulBackend* disc,
   cfg->stoppingWaitEvent = NonEvent;
   if (!validateRestarts(raw.find("restarts"), raw.find("when"), cfg, err))
     return false;
-  if (!validateSignalRestarts(raw.find("restarts"), cfg, err)) return false;
+  if (cfg->signal &&
+      !validateActionRestarts(raw.find("restarts"), "signal", cfg, err))
+    return false;
+  if (httpGiven &&
+      !validateActionRestarts(raw.find("restarts"), "http", cfg, err))
+    return false;
   if (!validateExec(raw, cfg, err)) return false;
+  if (httpGiven) {
+    // an action always runs under a deadline: the job's `timeout`, else
+    // `when.interval` (validateExec's rule for periodic jobs), else the
+    // blocking client's default
+    httpSpec.timeout = cfg->execTimeout > Duration(0)
+                           ? cfg->execTimeout
+                           : Duration(std::chrono::seconds(10));
+    cfg->http = std::make_shared<health::Probe>(std::move(httpSpec), cfg->name);
+  }
   *out = cfg;
   return true;
 }
@@ -607,6 +655,7 @@ Job::Job(const std::shared_ptr<JobConfig>& cfg)
     : name_(cfg->name),
       exec_(cfg->exec),
       signal_(cfg->signal),
+      http_(cfg->http),
       service_(cfg->serviceDefinition),
       healthCheckExec_(cfg->healthCheckExec),
       healthProbe_(cfg->healthProbe),
@@ -716,6 +765,16 @@ void Job::run(Loop& loop, std::shared_ptr<Bus> bus,
 
 void Job::kill() {
   if (exec_) exec_->kill();
+  if (http_ && http_->running()) {
+    http_->cancel();
+    // no exit event will follow: a pre/post-stop job that was kept for
+    // this one request ends here, so its stop chain moves on
+    if (phase_ == Phase::Running && loop_) {
+      restartsRemain_ = startsRemain_ = 0;
+      startEvent_ = NonEvent;
+      cleanup();
+    }
+  }
 }
 
 void Job::onEvent(const Event& event) {
@@ -812,11 +871,19 @@ void Job::startJobExec() {
   setStatus(JobStatus::Unknown);
   if (exec_) exec_->run(*loop_, bus_);
   else if (signal_) runSignalAction();
+  else if (http_) runHttpAction();
+}
+
+// the engine publishes the exit events itself, from source `<job>`, once
+// the response has been read out
+void Job::runHttpAction() {
+  if (ignoredWhileInFlight()) return;  // a `when.source: "SIGHUP"` start
+  http_->run(*loop_, bus_);
 }
 
 void Job::runSignalAction() {
   const signals::Spec& spec = signal_->spec;
-  if (ignoredDuringSignalWait()) return;  // a `when.source: "SIGHUP"` start
+  if (ignoredWhileInFlight()) return;  // a `when.source: "SIGHUP"` start
   // a target whose launch is still in flight has no pid yet
   pid_t pid = signal_->target ? signal_->target->pid() : -1;
   std::string reason;
@@ -893,9 +960,14 @@ Job::HandleResult Job::onStartTimeoutExpired() {
   return kContinue;
 }
 
-// A start that arrives while a signal job's `wait` is pending is ignored
-// before it can use up a start or a restart.
-bool Job::ignoredDuringSignalWait() const {
+// A start that arrives while a signal job's `wait` is pending, or an http
+// job's request is in flight, is ignored before it can use up a start or a
+// restart.
+bool Job::ignoredWhileInFlight() const {
+  if (http_ && http_->running()) {
+    LOG_DEBUG("%s: start ignored, request still in flight", name_.c_str());
+    return true;
+  }
   if (!signalWaiting_) return false;
   LOG_DEBUG("%s: start ignored, still waiting for %s to exit", name_.c_str(),
             signal_->spec.job.c_str());
@@ -903,7 +975,7 @@ bool Job::ignoredDuringSignalWait() const {
 }
 
 Job::HandleResult Job::onRunEveryTimerExpired() {
-  if (ignoredDuringSignalWait()) return kContinue;
+  if (ignoredWhileInFlight()) return kContinue;
   if (!restartPermitted()) {
     LOG_DEBUG("interval expired but restart not permitted: %s", name_.c_str());
     startEvent_ = NonEvent;
@@ -935,7 +1007,7 @@ Job::HandleResult Job::onQuit() {
   restartsRemain_ = 0;
   if ((startEvent_.code == EventCode::Stopping ||
        startEvent_.code == EventCode::Stopped) &&
-      (exec_ || signal_)) {
+      (exec_ || signal_ || http_)) {
     // pre-stop / post-stop jobs get one more start (jobs/jobs.go:295-308)
     if (startsRemain_ == kUnlimited) startsRemain_ = 1;
     return kContinue;
@@ -979,7 +1051,7 @@ Job::HandleResult Job::onSignalEvent(const std::string& sig) {
 }
 
 Job::HandleResult Job::onStartEvent() {
-  if (ignoredDuringSignalWait()) return kContinue;
+  if (ignoredWhileInFlight()) return kContinue;
   if (startsRemain_ == 0) {
     startEvent_ = NonEvent;
     return kHalt;
@@ -1046,6 +1118,7 @@ void Job::finishCleanup() {
   if (exec_ && exec_->running()) exec_->term();
   if (healthCheckExec_ && healthCheckExec_->running()) healthCheckExec_->term();
   if (healthProbe_ && healthProbe_->running()) healthProbe_->cancel();
+  if (http_ && http_->running()) http_->cancel();
 
   if (service_) service_->deregister();
   bus_->unsubscribe(this);

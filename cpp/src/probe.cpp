@@ -5,10 +5,13 @@
 #include <sys/epoll.h>
 #include <unistd.h>
 
+#include <strings.h>
+
 #include <cerrno>
 #include <cstring>
 
 #include "cpilot/decode.hpp"
+#include "cpilot/http.hpp"
 #include "cpilot/log.hpp"
 #include "cpilot/version.hpp"
 
@@ -174,17 +177,34 @@ bool parseTcpProbe(const std::string& hostPort, ProbeSpec* out,
   return parseAuthority(hostPort, 0, out, err);
 }
 
-bool parseHttpProbe(const Json& raw, ProbeSpec* out, std::string* errKey,
-                    std::string* err) {
+namespace {
+
+bool equalsIgnoreCase(const std::string& a, const char* b) {
+  return strcasecmp(a.c_str(), b) == 0;
+}
+
+// `health.http` and `jobs[].http` share every rule; an action adds the
+// methods that change state, `body`, and the refusal of the headers the
+// daemon sets itself
+bool parseHttpSpec(const Json& raw, bool action, ProbeSpec* out,
+                   std::string* errKey, std::string* err) {
   out->kind = ProbeSpec::Kind::Http;
+  out->action = action;
   errKey->clear();
-  if (raw.isString()) return parseProbeUrl(raw.str(), out, err);
+  if (raw.isString()) {
+    out->url = raw.str();
+    return parseProbeUrl(raw.str(), out, err);
+  }
   if (!raw.isObject()) {
     *err = "must be a URL string or an object";
     return false;
   }
-  if (!decode::checkKeys(raw, {"url", "method", "headers", "expect"}, err))
-    return false;
+  bool keysOk =
+      action ? decode::checkKeys(
+                   raw, {"url", "method", "headers", "expect", "body"}, err)
+             : decode::checkKeys(raw, {"url", "method", "headers", "expect"},
+                                 err);
+  if (!keysOk) return false;
 
   const Json* url = raw.find("url");
   if (!url || !url->isString() || url->str().empty()) {
@@ -196,15 +216,45 @@ bool parseHttpProbe(const Json& raw, ProbeSpec* out, std::string* errKey,
     *errKey = ".url";
     return false;
   }
+  out->url = url->str();
 
   if (const Json* method = raw.find("method")) {
-    if (!method->isString() ||
-        (method->str() != "GET" && method->str() != "HEAD")) {
+    bool ok = method->isString() &&
+              (method->str() == "GET" || method->str() == "HEAD");
+    if (action && !ok && method->isString())
+      for (const char* m : {"POST", "PUT", "PATCH", "DELETE"})
+        ok = ok || method->str() == m;
+    if (!ok) {
       *errKey = ".method";
-      *err = "must be 'GET' or 'HEAD'";
+      *err = action ? "must be one of 'GET', 'HEAD', 'POST', 'PUT', 'PATCH' "
+                      "or 'DELETE'"
+                    : "must be 'GET' or 'HEAD'";
       return false;
     }
     out->method = method->str();
+  }
+
+  if (const Json* body = action ? raw.find("body") : nullptr) {
+    if (!body->isNull()) {
+      *errKey = ".body";
+      if (!body->isString()) {
+        *err = "must be a string";
+        return false;
+      }
+      if (body->str().size() > kActionMaxBody) {
+        *err = "must be at most " + std::to_string(kActionMaxBody) +
+               " bytes, got " + std::to_string(body->str().size());
+        return false;
+      }
+      if (out->method == "GET" || out->method == "HEAD") {
+        *err = "cannot be sent with method '" + out->method +
+               "': use POST, PUT, PATCH or DELETE";
+        return false;
+      }
+      out->hasBody = true;
+      out->body = body->str();
+      errKey->clear();
+    }
   }
 
   if (const Json* headers = raw.find("headers")) {
@@ -229,6 +279,14 @@ bool parseHttpProbe(const Json& raw, ProbeSpec* out, std::string* errKey,
         *err = "names must be non-empty and free of ':' and whitespace";
         return false;
       }
+      if (action)
+        for (const char* own : {"Host", "Connection", "Content-Length",
+                                "Transfer-Encoding"})
+          if (equalsIgnoreCase(kv.first, own)) {
+            *err = "'" + kv.first + "' is set by the daemon and cannot be "
+                   "configured";
+            return false;
+          }
       out->headers.emplace_back(kv.first, kv.second.str());
     }
     errKey->clear();
@@ -264,14 +322,31 @@ bool parseHttpProbe(const Json& raw, ProbeSpec* out, std::string* errKey,
   return true;
 }
 
+}  // namespace
+
+bool parseHttpProbe(const Json& raw, ProbeSpec* out, std::string* errKey,
+                    std::string* err) {
+  return parseHttpSpec(raw, false, out, errKey, err);
+}
+
+bool parseHttpAction(const Json& raw, ProbeSpec* out, std::string* errKey,
+                     std::string* err) {
+  return parseHttpSpec(raw, true, out, errKey, err);
+}
+
 std::string buildProbeRequest(const ProbeSpec& spec) {
   std::string req = spec.method + " " + spec.path + " HTTP/1.1\r\n";
   req += "Host: " + spec.hostHeader + "\r\n";
   req += std::string("User-Agent: containerpilot/") + kVersion + "\r\n";
   req += "Accept: */*\r\n";
   req += "Connection: close\r\n";
+  // a length-less POST, PUT or PATCH is refused (411) by many servers
+  if (spec.hasBody || spec.method == "POST" || spec.method == "PUT" ||
+      spec.method == "PATCH")
+    req += "Content-Length: " + std::to_string(spec.body.size()) + "\r\n";
   for (auto& kv : spec.headers) req += kv.first + ": " + kv.second + "\r\n";
   req += "\r\n";
+  req += spec.body;
   return req;
 }
 
@@ -309,6 +384,11 @@ void Probe::run(Loop& loop, std::shared_ptr<Bus> bus) {
   bus_ = std::move(bus);
   sent_ = 0;
   rbuf_.clear();
+  code_ = 0;
+  verdict_.clear();
+  drained_ = 0;
+  headDone_ = bodyKnown_ = false;
+  bodyEnd_ = 0;
 
   fd_ = socket(spec_.addr.ss_family, SOCK_STREAM | SOCK_NONBLOCK | SOCK_CLOEXEC,
                0);
@@ -353,13 +433,17 @@ void Probe::cancel() {
   teardown();
 }
 
-std::shared_ptr<Bus> Probe::teardown() {
+std::shared_ptr<Bus> Probe::teardown(bool orderly) {
   if (fd_ >= 0) {
     if (state_ != State::Idle) loop_->unwatchFd(fd_);
     // abortive close: the daemon always closes first, so an orderly
-    // close would park every check's port in TIME_WAIT on this side
-    struct linger lg = {1, 0};
-    setsockopt(fd_, SOL_SOCKET, SO_LINGER, &lg, sizeof(lg));
+    // close would park every check's port in TIME_WAIT on this side.
+    // After the peer's FIN the peer closed first and holds the TIME_WAIT,
+    // so an action that read its response out closes orderly.
+    if (!orderly) {
+      struct linger lg = {1, 0};
+      setsockopt(fd_, SOL_SOCKET, SO_LINGER, &lg, sizeof(lg));
+    }
     close(fd_);
     fd_ = -1;
   }
@@ -380,7 +464,8 @@ void Probe::pass() {
 
 void Probe::fail(const std::string& reason, bool timedOut) {
   auto bus = teardown();
-  if (timedOut)
+  // a failed action is the job's own outcome, like a non-zero exit
+  if (timedOut || spec_.action)
     LOG_WARN("%s: %s", name_.c_str(), reason.c_str());
   else
     LOG_ERROR("%s: %s", name_.c_str(), reason.c_str());
@@ -400,6 +485,11 @@ void Probe::failErrno(int err) {
 
 void Probe::onTimeout() {
   if (!running()) return;
+  if (state_ == State::Draining) {
+    // the verdict was decided at the status line and stands
+    finishDrain(false);
+    return;
+  }
   fail("timeout after " + probeDurationString(spec_.timeout), true);
 }
 
@@ -436,6 +526,9 @@ void Probe::onIo(uint32_t events) {
       break;
     case State::Reading:
       onReadable();
+      break;
+    case State::Draining:
+      onDrainReadable();
       break;
     case State::Idle:
       break;
@@ -520,8 +613,107 @@ void Probe::judgeStatusLine(size_t crlf) {
   } else {
     for (int want : spec_.expect) ok = ok || want == code;
   }
+  if (spec_.action) {
+    code_ = code;
+    if (!ok) verdict_ = "unexpected status " + std::to_string(code);
+    beginDrain(crlf);
+    return;
+  }
   if (ok) pass();
   else fail("unexpected status " + std::to_string(code));
+}
+
+// ---------------- actions: read the response out ----------------
+//
+// The verdict stands from the status line on. The server is doing real
+// work for an action, and a reset while it writes its response is an error
+// in its log, so the rest is read and discarded until the peer closes, the
+// announced Content-Length has arrived, kActionMaxDrain bytes went by or
+// the deadline hits, whichever is first.
+
+void Probe::beginDrain(size_t crlf) {
+  state_ = State::Draining;
+  drained_ = rbuf_.size();
+  // rbuf_ keeps the head (from the status line's CRLF on) until it ends
+  rbuf_.erase(0, crlf);
+  if (drainComplete()) {
+    finishDrain(false);
+    return;
+  }
+  onDrainReadable();
+}
+
+// called after every read: looks for the end of the head once, then only
+// compares counters
+bool Probe::drainComplete() {
+  if (!headDone_) {
+    // rbuf_ starts at the status line's CRLF, so a response without
+    // header lines ends its head right there
+    size_t end = rbuf_.find("\r\n\r\n");
+    if (end != std::string::npos) {
+      headDone_ = true;
+      http::Headers headers;
+      http::parseHeaderLines(rbuf_, 2, end, &headers);
+      size_t headEnd = drained_ - (rbuf_.size() - (end + 4));
+      bool noBody = spec_.method == "HEAD" || code_ < 200 || code_ == 204 ||
+                    code_ == 304;
+      if (noBody) {
+        bodyKnown_ = true;
+        bodyEnd_ = headEnd;
+      } else if (!http::isChunked(headers) && headers.count("content-length")) {
+        size_t len = http::contentLength(headers);
+        bodyKnown_ = true;
+        // a length that wraps is one the cap ends
+        bodyEnd_ = len > kActionMaxDrain ? kActionMaxDrain + 1 : headEnd + len;
+      }
+      rbuf_.clear();
+    } else if (rbuf_.size() > kActionMaxHead) {
+      // no length will be learnt from a head this long: the response
+      // ends at close or at the cap
+      headDone_ = true;
+      rbuf_.clear();
+    }
+  }
+  if (bodyKnown_ && drained_ >= bodyEnd_) return true;
+  return drained_ >= kActionMaxDrain;
+}
+
+void Probe::onDrainReadable() {
+  char buf[16384];
+  while (true) {
+    ssize_t n = recv(fd_, buf, sizeof(buf), 0);
+    if (n > 0) {
+      drained_ += (size_t)n;
+      if (!headDone_) rbuf_.append(buf, (size_t)n);
+      if (drainComplete()) {
+        finishDrain(false);
+        return;
+      }
+    } else if (n == 0) {
+      finishDrain(true);
+      return;
+    } else if (errno == EINTR) {
+      continue;
+    } else if (errno == EAGAIN || errno == EWOULDBLOCK) {
+      return;
+    } else {
+      finishDrain(false);  // reset by the peer: nothing more will come
+      return;
+    }
+  }
+}
+
+void Probe::finishDrain(bool peerClosed) {
+  auto bus = teardown(peerClosed);
+  if (verdict_.empty()) {
+    LOG_INFO("%s: %s %s answered %d", name_.c_str(), spec_.method.c_str(),
+             spec_.url.c_str(), code_);
+    bus->publish(Event{EventCode::ExitSuccess, name_});
+    return;
+  }
+  LOG_WARN("%s: %s", name_.c_str(), verdict_.c_str());
+  bus->publish(Event{EventCode::ExitFailed, name_});
+  bus->publish(Event{EventCode::Error, name_ + ": " + verdict_});
 }
 
 }  // namespace health

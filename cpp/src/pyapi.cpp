@@ -12,6 +12,7 @@
 #include "cpilot/config.hpp"
 #include "cpilot/control.hpp"
 #include "cpilot/discovery.hpp"
+#include "cpilot/jobs.hpp"
 #include "cpilot/json.hpp"
 #include "cpilot/sensor.hpp"
 #include "cpilot/signals.hpp"
@@ -249,6 +250,35 @@ int cp_signal_number(const char* name, char** errOut) {
                         "' is not accepted: must be one of " +
                         signals::acceptedNames());
   return -1;
+}
+
+// The exact bytes the http job `jobJson` (one entry of `jobs`) would write
+// to its target: a malloc'd buffer of *outLen bytes, since a body may hold
+// any byte. nullptr + *errOut with the config error of a refused job, or
+// for a job without `http`.
+char* cp_http_action_request(const char* jobJson, size_t* outLen,
+                             char** errOut) {
+  try {
+    std::shared_ptr<JobConfig> cfg;
+    std::string err;
+    if (!validateJobConfig(parseJson5(jobJson), nullptr, &cfg, &err)) {
+      if (errOut) *errOut = dupString(err);
+      return nullptr;
+    }
+    if (!cfg->http) {
+      if (errOut) *errOut = dupString("job[" + cfg->name + "] has no 'http'");
+      return nullptr;
+    }
+    std::string out = health::buildProbeRequest(cfg->http->spec());
+    char* buf = (char*)malloc(out.size() + 1);
+    memcpy(buf, out.data(), out.size());
+    buf[out.size()] = '\0';
+    if (outLen) *outLen = out.size();
+    return buf;
+  } catch (const std::exception& e) {
+    if (errOut) *errOut = dupString(e.what());
+    return nullptr;
+  }
 }
 
 // Replay a script against the daemon's own metrics path, in a registry of

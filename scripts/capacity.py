@@ -27,10 +27,19 @@ Env: CPILOT_CAPACITY_WATCHES (default 0), CPILOT_CAPACITY_WINDOW (20s),
      deliveries of the daemon plus all its descendants. native uses
      `jobs[].signal`; exec is the only way without it: a job running
      `/bin/sh -c 'kill -HUP $CONTAINERPILOT_NGINX_PID'`.
+     CPILOT_CAPACITY_HTTPJOBS = native | exec (default unset): instead of
+     the stress shape, N periodic jobs (the arguments are job counts,
+     default 10) each POST to one bin/cpilot_probesink every
+     CPILOT_CAPACITY_HTTPJOB_MS (100); reports CPU seconds per 1000
+     actions, of the daemon process alone and of the daemon plus all its
+     descendants. native uses `jobs[].http`; exec is the only way without
+     it: a job running `curl --fail -s -XPOST`. Without a `curl` on the
+     machine the exec side is skipped, and says so.
 """
 import json
 import os
 import re
+import shutil
 import stat
 import sys
 import tempfile
@@ -206,6 +215,80 @@ def signal_capacity(mode, count, every_ms):
     }), flush=True)
     d.cleanup()
 
+
+def httpjob_capacity(mode, count, every_ms):
+    curl = shutil.which("curl")
+    if mode == "exec" and not curl:
+        print(json.dumps({"httpjobs": "exec", "skipped": "no curl here"}),
+              flush=True)
+        return
+    wd = tempfile.mkdtemp()
+    port = free_port()
+    # the sink answers with a length and closes: its cost is the same in
+    # both modes and it is no descendant of the daemon
+    sink = harness.ProbeSink("http200").start()
+    url = "http://127.0.0.1:%d/-/reload" % sink.port
+    jobs = []
+    for i in range(count):
+        job = {"name": "reload-%03d" % i,
+               "when": {"interval": "%dms" % every_ms}}
+        if mode == "native":
+            job["http"] = {"url": url, "method": "POST"}
+        else:
+            job["exec"] = [curl, "--fail", "-s", "-o", "/dev/null",
+                           "-XPOST", url]
+        jobs.append(job)
+    d = harness.Daemon(config_dict={
+        "consul": "localhost:79", "stopTimeout": 1,
+        "logging": {"level": "ERROR"}, "jobs": jobs,
+        "telemetry": {"port": port, "interfaces": ["static:127.0.0.1"]}},
+        workdir=wd)
+    d.start()
+    d.wait_for_socket(timeout=60)
+
+    def actions():
+        target = "http://127.0.0.1:%d/metrics" % port
+        with urllib.request.urlopen(target, timeout=10) as resp:
+            text = resp.read().decode()
+        pattern = (r'^containerpilot_events\{code="ExitSuccess",'
+                   r'source="reload-\d+"\} (\S+)$')
+        return sum(float(v) for v in re.findall(pattern, text, re.M))
+
+    def cpu():
+        return cpu_seconds(d.proc.pid), tree_cpu_seconds(d.proc.pid)
+
+    time.sleep(warmup)
+    n0, (c0, tree0), t0 = actions(), cpu(), time.time()
+    time.sleep(window)
+    n1, (c1, tree1), el = actions(), cpu(), time.time() - t0
+
+    def per_1000(seconds):
+        return round(1000.0 * seconds / (n1 - n0), 4) if n1 > n0 else None
+
+    print(json.dumps({
+        "httpjobs": mode,
+        "jobs": count,
+        "interval_ms": every_ms,
+        "window_sec": round(el, 2),
+        "actions": round(n1 - n0),
+        "actions_per_sec": round((n1 - n0) / el, 1),
+        "daemon_cpu_sec": round(c1 - c0, 3),
+        "tree_cpu_sec": round(tree1 - tree0, 3),
+        "daemon_cpu_sec_per_1000_actions": per_1000(c1 - c0),
+        "tree_cpu_sec_per_1000_actions": per_1000(tree1 - tree0),
+    }), flush=True)
+    d.cleanup()
+    sink.stop()
+
+
+httpjobs_mode = os.environ.get("CPILOT_CAPACITY_HTTPJOBS")
+if httpjobs_mode:
+    if httpjobs_mode not in ("native", "exec"):
+        sys.exit("CPILOT_CAPACITY_HTTPJOBS must be native or exec")
+    every = int(os.environ.get("CPILOT_CAPACITY_HTTPJOB_MS", "100"))
+    for count in [int(a) for a in sys.argv[1:]] or [10]:
+        httpjob_capacity(httpjobs_mode, count, every)
+    sys.exit(0)
 
 signals_mode = os.environ.get("CPILOT_CAPACITY_SIGNALS")
 if signals_mode:
